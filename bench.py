@@ -8,6 +8,18 @@ GPU over RCCL.  W untimed warmup steps, then exactly K timed steps bracketed
 by barrier + torch.cuda.synchronize() on both sides; wall time is the MAX
 over ranks; rank 0 prints one JSON line.
 
+A plain run does only that: set up, warm up, time the K steps, print the
+result line.  Two options add to it:
+    --dump-outputs DIR  after the timed steps, rank 0 writes what the last
+                        timed step computed as DIR/<name>.npy (see
+                        dump_outputs below).  Weights, batch and sample
+                        indices are seeded, so two builds run with the same
+                        arguments can be compared array for array.
+    --full              also run the auxiliary measurements.  There are none
+                        today (every other figure of the project comes from
+                        scripts/ and profiles/); anything added later that the
+                        headline figure does not need belongs behind it.
+
 Metric: whole-job training throughput in tokens/s, bf16, synthetic data
 (random token ids + random taxonomy labels, random-init weights — there is no
 network for datasets).  The reference publishes no performance numbers
@@ -55,6 +67,38 @@ elif os.path.exists(_TUNE_FILE.replace(".csv", "0.csv")) and \
 
 import torch
 
+_INIT_SEED = 1234            # weight init (the batch uses 1234 + rank)
+_DUMP_SEED = 4321            # which flat-buffer elements --dump-outputs keeps
+_DUMP_SAMPLE = 1 << 20       # elements per dumped array (4 MB as float32)
+
+
+def dump_outputs(out_dir: str, trainer, loss: float) -> None:
+    """Write the results of the last timed step as <out_dir>/<name>.npy.
+
+    trainer.step() hands the caller the loss and leaves the gradients and the
+    updated weights in the trainer's flat buffers, so those are the outputs:
+    loss (float64, shape [1]) and float32 copies of grads (bf16 flat
+    gradient), params (bf16 flat weights) and master (f32 master weights).
+    The flagship model's flat buffers are far larger than a dump should be,
+    so each is cut to the same fixed, seeded, sorted sample of _DUMP_SAMPLE
+    element indices (whole buffer when it is smaller)."""
+    import numpy as np
+    flat = trainer.flat
+    n = flat.numel
+    if n > _DUMP_SAMPLE:
+        g = torch.Generator(device="cpu").manual_seed(_DUMP_SEED)
+        idx = torch.randint(0, n, (_DUMP_SAMPLE,), generator=g)
+        idx = idx.sort().values.to(flat.flat.device)
+    else:
+        idx = torch.arange(n, device=flat.flat.device)
+    arrays = {"loss": np.asarray([loss], dtype=np.float64)}
+    for name, buf in (("grads", flat.grad_flat), ("params", flat.flat),
+                      ("master", flat.master)):
+        arrays[name] = buf[idx].float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
 
 def main() -> None:
     ap = argparse.ArgumentParser()
@@ -65,7 +109,13 @@ def main() -> None:
     ap.add_argument("--seq", type=int, default=512)
     ap.add_argument("--model", type=str, default="mltc-base")
     ap.add_argument("--bucket-mb", type=int, default=64)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run auxiliary measurements (none today)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -96,6 +146,7 @@ def main() -> None:
     tcfg = TrainConfig(model=args.model, warmup_steps=0,
                        total_steps=max(args.steps * 100, 1000),
                        bucket_mb=args.bucket_mb)
+    torch.manual_seed(_INIT_SEED)   # same initial weights on every run
     trainer = Trainer(tcfg, device=device, model_cfg=cfg)
 
     tokens, mask, labels = synthetic_batch(
@@ -113,9 +164,12 @@ def main() -> None:
     barrier_sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        trainer.step(tokens, mask, labels)
+        loss = trainer.step(tokens, mask, labels)
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss)
 
     # MAX over ranks
     if world > 1:

@@ -39,10 +39,12 @@ def test_split_seed_pins_partition():
 
 def test_ensemble_probs_script(tmp_path):
     """scripts/ensemble_probs.py: shared-gold verification + averaging."""
+    import os
     import subprocess
     import sys
 
     import torch
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     g = torch.Generator().manual_seed(0)
     gold = {"strategy": (torch.rand(20, 19, generator=g) < 0.2).float(),
             "property": (torch.rand(20, 21, generator=g) < 0.2).float()}
@@ -55,7 +57,7 @@ def test_ensemble_probs_script(tmp_path):
         paths.append(str(p))
     out = subprocess.run(
         [sys.executable, "scripts/ensemble_probs.py"] + paths,
-        capture_output=True, text=True, cwd="/root/repo")
+        capture_output=True, text=True, cwd=repo)
     assert out.returncode == 0, out.stderr
     assert "ENSEMBLE x2" in out.stdout
     # mismatched gold must abort
@@ -65,5 +67,5 @@ def test_ensemble_probs_script(tmp_path):
     torch.save(bad, pb)
     out2 = subprocess.run(
         [sys.executable, "scripts/ensemble_probs.py", paths[0], str(pb)],
-        capture_output=True, text=True, cwd="/root/repo")
+        capture_output=True, text=True, cwd=repo)
     assert out2.returncode != 0
