@@ -1,64 +1,247 @@
-// Flash-attention forward for gfx950 (CDNA4) — bf16 I/O, f32 online softmax,
-// MFMA (v_mfma_f32_32x32x16_bf16) for QK^T and PV, head_dim = 64.
+// Flash attention for gfx950 (CDNA4) — bf16 I/O, f32 online softmax, MFMA
+// (v_mfma_f32_32x32x16_bf16) everywhere, head_dim = 64.
 //
-// Never materializes the [L, L] score matrix: per 32-row Q block (one wave),
-// iterate 32-key KV tiles with the running-max/denominator recurrence and
-// accumulate O in registers.  Saves the per-row logsumexp for the recompute
-// backward (tosem2021_amd/ops: bwd = bmm-recompute + softmax_bwd).
+// Never materializes the [L, L] score matrix.  Four MFMA kernels:
+//   flash_fwd_kernel           O and the per-row logsumexp
+//   flash_bwd_fused_kernel     dK, dV (one wave per 32-row kv block)
+//   flash_dq_recompute_kernel  dQ, recomputing S/dP/dS in registers
+//   flash_dq_kernel            dQ = dS @ K from a materialized dS (A/B path)
+// plus fa_dot (D = rowsum(dO * O)).  The default backward is
+// fa_dot + flash_bwd_fused + flash_dq_recompute.
 //
-// Structure (guide §B "fused attention prefill" adapted):
+// Shared structure (guide §B "fused attention prefill" adapted):
 //  * swapped QK^T — compute mfma(A=K, B=Q^T) so the score column for one
 //    q-row is LANE-LOCAL (16 regs + the partner lane at lane^32): softmax is
 //    15 in-lane max/sum ops + one __shfl_xor(32) exchange, no LDS round trip.
-//  * P -> PV A-fragments via v_cvt_pk_bf16_f32 pairs + permlane32_swap
+//  * C-layout -> A-fragments via v_cvt_pk_bf16_f32 pairs + permlane32_swap
 //    (guide T12): 8 cvt_pk + 4 swaps replace any cross-lane scatter.
-//  * K tile staged row-major in LDS with the T2 XOR swizzle
-//    (byte ^= (row&7)<<4) so the fragment ds_read_b128 is ~conflict-free;
-//    V tile staged TRANSPOSED ([64 d][32 kv], 80 B row stride) so the PV
-//    B-fragment is a clean ds_read_b128 as well.
-//  * workgroup = 4 waves = 128 q rows of one (b, h); K/V tiles staged once
-//    per workgroup and consumed by all four waves.
+//  * every staged tile (K, V, Q, dO) is [32][64] bf16 row-major in LDS with
+//    the T2 XOR swizzle (byte ^= (row&7)<<4): the row-fragment ds_read_b128
+//    is ~conflict-free, and the TRANSPOSED fragment of the same tile is
+//    gathered with ds_read_b64_tr_b16 — no second, transposed copy.
+//  * workgroup = 4 waves sharing the staged tiles.  In the q-major kernels
+//    (fwd, dq, dq-recompute) each wave owns TWO 32-row q-blocks, so a
+//    workgroup covers 256 q rows; in flash_bwd_fused each wave owns one
+//    32-row kv block, so a workgroup covers 128 kv rows.
 
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(2))) unsigned uint2_t;
+typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
 
 #define FA_DH 64
 #define FA_KVB 32
-#define FA_QB 32          // q rows per wave
+#define FA_QB 32          // q rows per q-block
 #define FA_WAVES 4
 #define FA_BLOCK (FA_WAVES * WAVE)
-#define FA_QWG (FA_WAVES * FA_QB)   // 128 q rows per workgroup
+#define FA_QWG (FA_WAVES * FA_QB)   // 128 rows: one 32-row block per wave
+#define FA_Q2WG (2 * FA_QWG)        // 256 q rows: two q-blocks per wave
 
-// LDS layout (dynamic, 16-B aligned):
-//  K tile: [32][64] bf16, row stride 128 B, XOR-swizzled       = 4096 B
-//  V tile: same layout — the PV B-fragment is gathered with
-//          ds_read_b64_tr_b16 (lane-grid-transpose semantics pinned by
-//          scripts/tr_probe.py; see the PV block below)         = 4096 B
-//  alpha:  [4 waves][32] f32                                   =  512 B
-#define K_LDS_BYTES (FA_KVB * 128)
-#define VT_LDS_BYTES (FA_KVB * 128)
+// LDS (dynamic, 16-B aligned).  One staged tile is [32][64] bf16, row
+// stride 128 B, XOR-swizzled = 4096 B.  Per kernel:
+//  fwd:          K tile | V tile | alpha [4 waves][64] f32 (1024 B; its
+//                first word doubles as the tail-skip scratch before the loop)
+//  bwd_fused:    Q tile | dO tile | lse [32] f32 | ddot [32] f32
+//  dq:           K tile
+//  dq_recompute: K tile | V tile | 16 B tail-skip scratch
+#define TILE_LDS_BYTES (FA_KVB * 128)
+#define FWD_LDS_BYTES (2 * TILE_LDS_BYTES + FA_WAVES * 64 * sizeof(float))
+#define BWD_LDS_BYTES (2 * TILE_LDS_BYTES + 64 * sizeof(float))
+#define DQ_LDS_BYTES TILE_LDS_BYTES
+#define DQR_LDS_BYTES (2 * TILE_LDS_BYTES + 16)
+
+// Tensor geometry: the kernels address q/k/v rows as
+//   base + b*qkv_bs + h*qkv_hs + l*qkv_rs        (64 contiguous shorts)
+// and o/dout rows as b*o_bs + h*o_hs + l*o_rs — so the SAME kernels run on
+// the bmm-style [B, H, L, 64] layout and directly on the packed
+// QKV-projection output [B, L, 3D] (k/v at base offset D/2D) with the
+// attention output written straight into the [B, L, D] proj input.  The
+// packed path deletes the four qkv/out repack kernels (+their backward
+// merges) from the model step.
+struct FaGeom {
+  long qkv_bs, qkv_hs; int qkv_rs;
+  long o_bs, o_hs; int o_rs;
+  static FaGeom bhld(int H, int L) {        // q/k/v/o all [B, H, L, 64]
+    return {(long)H * L * FA_DH, (long)L * FA_DH, FA_DH,
+            (long)H * L * FA_DH, (long)L * FA_DH, FA_DH};
+  }
+  static FaGeom packed(int H, int L) {      // qkv [B, L, 3D], o [B, L, D]
+    const int D = H * FA_DH;
+    return {(long)L * 3 * D, 64L, 3 * D, (long)L * D, 64L, D};
+  }
+};
+
+// ---- fragment plumbing shared by the four MFMA kernels ----------------------
+// All of it encodes the 32x32x16 MFMA register layouts and the lane-grid
+// law of ds_read_b64_tr_b16 pinned by scripts/tr_probe.py; a tile-layout or
+// swizzle change is made here, once.
 
 __device__ __forceinline__ int kswz(int row, int byte_off) {
   return byte_off ^ ((row & 7) << 4);
 }
 
-// Tensor geometry (round 2): the kernels address q/k/v rows as
-//   base + b*qkv_bs + h*qkv_hs + l*qkv_rs        (64 contiguous shorts)
-// and o/dout rows as b*o_bs + h*o_hs + l*o_rs — so the SAME kernels run on
-// the bmm-style [B, H, L, 64] layout (qkv_bs=H*L*64, qkv_hs=L*64,
-// qkv_rs=64) and directly on the packed QKV-projection output [B, L, 3D]
-// (qkv_bs=L*3D, qkv_hs=64, qkv_rs=3D, k/v base-offset D/2D) with the
-// attention output written straight into the [B, L, D] proj input
-// (o_bs=L*D, o_hs=64, o_rs=D).  The packed path deletes the four
-// qkv/out repack kernels (+their backward merges) from the model step.
+// C-layout row map: accumulator register r of the lane half `half` holds
+// row c_row(r, half) of the 32x32 result (the lane's column is lane & 31).
+__device__ __forceinline__ int c_row(int r, int half) {
+  return (r & 3) + 8 * (r >> 2) + 4 * half;
+}
 
-// Padding-tail tile skip (round 2): with the additive -1e9 padding bias,
-// every score in a fully-masked kv tile sits below ~-1e8 and __expf
-// underflows to exactly +0.0f, so the tile contributes NOTHING to the
-// online softmax (alpha==1, rowsum+=0, O+=0) or to dQ — identical to not
-// running it.  The mask is per-(batch, kv) so the last unmasked position
-// is workgroup-uniform; tiles past it are skipped.  If the whole row is
+// Tile staging: 256 threads move one [32][64] bf16 tile, 16 B each.  load()
+// reads this thread's piece of the tile starting at global row `row0` (rows
+// `rs` shorts apart) into a register — issued one tile ahead as the
+// prefetch — and store() writes it to the swizzled LDS tile.
+struct FaStager {
+  int row, byte;
+  __device__ __forceinline__ explicit FaStager(int tid)
+      : row(tid >> 3), byte((tid & 7) * 16) {}
+  __device__ __forceinline__ short8_t load(const short* base, int row0,
+                                           int rs) const {
+    return *(const short8_t*)(base + (long)(row0 + row) * rs + (byte >> 1));
+  }
+  __device__ __forceinline__ void store(short* lds, short8_t v) const {
+    *(short8_t*)((char*)lds + row * 128 + kswz(row, byte)) = v;
+  }
+};
+
+// Row fragment c (k = 16c .. 16c+15) of a staged tile: lane reads 8 bf16 of
+// tile row `col` — the A operand of the S/dP MFMAs.
+__device__ __forceinline__ short8_t tile_row_frag(const short* lds, int col,
+                                                  int half, int c) {
+  return *(const short8_t*)((const char*)lds + col * 128 +
+                            kswz(col, (16 * c + 8 * half) * 2));
+}
+
+// C-layout f32 (reg=R, lane=C) -> bf16 A-fragments [row=C][k=R].  One step
+// packs registers r0, r0+1 and r1, r1+1 and swaps lane halves; it yields
+// words i and i+2 of the fragment.  permlane32_swap needs two wait states
+// after a VALU write and hipcc pads only one after inline asm, hence the
+// explicit s_nop 1.
+__device__ __forceinline__ void cvt_pk_swap(const float (&s)[16], int r0,
+                                            int r1, uint4_t& u, int i) {
+  unsigned lo, hi;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(lo)
+      : "v"(s[r0]), "v"(s[r0 + 1]));
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(hi)
+      : "v"(s[r1]), "v"(s[r1 + 1]));
+  auto sw = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
+  u[i] = sw[0]; u[i + 2] = sw[1];
+}
+
+// Every kernel repacks TWO accumulators at the same point (q-blocks A and
+// B, or P and dS).  Their steps alternate, so the scheduler sees two
+// independent cvt -> swap chains side by side; repacking one accumulator
+// wholly before the other gives a different (measured: not faster) loop
+// schedule.
+__device__ __forceinline__ void c_to_afrag2(const float (&sa)[16],
+                                            short8_t (&fa)[2],
+                                            const float (&sb)[16],
+                                            short8_t (&fb)[2]) {
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    uint4_t ua, ub;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int r0 = c * 8 + 2 * i;
+      int r1 = c * 8 + 4 + 2 * i;
+      cvt_pk_swap(sa, r0, r1, ua, i);
+      cvt_pk_swap(sb, r0, r1, ub, i);
+    }
+    fa[c] = __builtin_bit_cast(short8_t, ua);
+    fb[c] = __builtin_bit_cast(short8_t, ub);
+  }
+}
+
+// Transposed fragments of a staged [32][64] tile X: the B operands
+// X^T[d][row] for both 32-wide d halves (t) and both 16-row k chunks (c),
+// gathered with eight ds_read_b64_tr_b16 lane-grid transpose reads.
+struct FaTrFrags {
+  uint2_t r[8];
+  __device__ __forceinline__ short8_t frag(int c, int t) const {
+    uint4_t w;
+    w[0] = r[c * 4 + 0 * 2 + t][0];
+    w[1] = r[c * 4 + 0 * 2 + t][1];
+    w[2] = r[c * 4 + 1 * 2 + t][0];
+    w[3] = r[c * 4 + 1 * 2 + t][1];
+    return __builtin_bit_cast(short8_t, w);
+  }
+};
+
+// tr_offsets gives the lane's eight byte offsets into a tile.  They are the
+// same for every staged tile and every loop iteration, so a kernel takes
+// them once, up front.
+struct FaTrOffsets { unsigned a[8]; };
+
+__device__ __forceinline__ FaTrOffsets tr_offsets(int lane, int half) {
+  const int row_mate = (lane >> 2) & 3;
+  const int d_lane = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  FaTrOffsets o;
+#pragma unroll
+  for (int c = 0; c < 2; ++c)
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        int row = 16 * c + 8 * half + 4 * rr + row_mate;
+        int dcol = (32 * t + d_lane) * 2;
+        o.a[c * 4 + rr * 2 + t] = row * 128 + kswz(row, dcol);
+      }
+  return o;
+}
+
+// tr_issue adds the tile's LDS base and issues the eight reads with their
+// s_waitcnt in ONE asm volatile, so the compiler can neither split the batch
+// nor sink the wait.
+__device__ __forceinline__ void tr_issue(const short* lds,
+                                         const FaTrOffsets& o, FaTrFrags& f) {
+  const unsigned base = (unsigned)(unsigned long)(char*)lds;
+  unsigned a[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) a[i] = base + o.a[i];
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %8\n\t"
+      "ds_read_b64_tr_b16 %1, %9\n\t"
+      "ds_read_b64_tr_b16 %2, %10\n\t"
+      "ds_read_b64_tr_b16 %3, %11\n\t"
+      "ds_read_b64_tr_b16 %4, %12\n\t"
+      "ds_read_b64_tr_b16 %5, %13\n\t"
+      "ds_read_b64_tr_b16 %6, %14\n\t"
+      "ds_read_b64_tr_b16 %7, %15\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(f.r[0]), "=&v"(f.r[1]), "=&v"(f.r[2]), "=&v"(f.r[3]),
+        "=&v"(f.r[4]), "=&v"(f.r[5]), "=&v"(f.r[6]), "=&v"(f.r[7])
+      : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]),
+        "v"(a[6]), "v"(a[7])
+      : "memory");
+}
+
+// The gather proper: the reads, then a scheduling fence so the MFMA chain
+// that consumes the fragments is not hoisted above them.  A kernel that
+// gathers two tiles back to back (flash_bwd_fused) issues the first with
+// tr_issue and fences once, after the second.
+__device__ __forceinline__ void tr_gather(const short* lds,
+                                          const FaTrOffsets& o, FaTrFrags& f) {
+  tr_issue(lds, o, f);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// Work split of the q-major kernels: workgroup -> (b*H + h, 256-row q
+// chunk), wave -> q-blocks A = rows [qA, qA+32) and B = [qB, qB+32).
+struct FaQBlocks { int bh, qA, qB; };
+
+__device__ __forceinline__ FaQBlocks fa_qblocks(int L, int wid) {
+  const int n_qblocks = (L + FA_Q2WG - 1) / FA_Q2WG;
+  const int bid = xcd_group_remap(blockIdx.x, gridDim.x, n_qblocks);
+  const int qA = (bid % n_qblocks) * FA_Q2WG + wid * FA_QB;
+  return {bid / n_qblocks, qA, qA + FA_QWG};
+}
+
+// Padding-tail tile skip: with the additive -1e9 padding bias, every score
+// in a fully-masked kv tile sits below ~-1e8 and __expf underflows to
+// exactly +0.0f, so the tile contributes NOTHING to the online softmax
+// (alpha==1, rowsum+=0, O+=0) or to dQ — identical to not running it.  The
+// mask is per-(batch, kv) so the last unmasked position is
+// workgroup-uniform; tiles past it are skipped.  If the whole row is
 // masked (last==-1) nothing is skipped, preserving the reference
 // softmax-over-bias behavior for degenerate all-pad sequences.
 __device__ __forceinline__ int fa_last_active_kv(const float* mrow, int L,
@@ -77,46 +260,37 @@ extern "C" __global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
                  const short* __restrict__ v, const float* __restrict__ mask,
                  short* __restrict__ o, float* __restrict__ lse,
-                 int B, int H, int L, float scale,
-                 long qkv_bs, long qkv_hs, int qkv_rs,
-                 long o_bs, long o_hs, int o_rs) {
+                 int B, int H, int L, float scale, FaGeom g) {
   // Each wave processes TWO independent 32-row q-blocks against the shared
   // K/V tile: the second block's MFMAs overlap the first block's serial
-  // softmax chain (ILP within the wave).  2 waves/SIMD by registers; the
-  // workgroup covers 256 q rows.
+  // softmax chain (ILP within the wave).  2 waves/SIMD by registers.
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  short* k_lds = (short*)smem;                       // swizzled [32][64]
-  short* v_lds = (short*)(smem + K_LDS_BYTES);       // swizzled [32][64]
-  float* alpha_lds = (float*)(smem + K_LDS_BYTES + VT_LDS_BYTES);
+  short* k_lds = (short*)smem;
+  short* v_lds = (short*)(smem + TILE_LDS_BYTES);
+  float* alpha_lds = (float*)(smem + 2 * TILE_LDS_BYTES);
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wid = tid / WAVE;
   const int col = lane & 31;
   const int half = lane >> 5;
+  const FaTrOffsets tro = tr_offsets(lane, half);
 
-  const int rows_per_wg = 2 * FA_QWG;                 // 256
-  const int n_qblocks = (L + rows_per_wg - 1) / rows_per_wg;
-  int bid = xcd_group_remap(blockIdx.x, gridDim.x, n_qblocks);
-  int bh = bid / n_qblocks;
-  int qb = bid % n_qblocks;
-  const int b = bh / H;
-  const int h = bh % H;
-  const long qkv_off = (long)b * qkv_bs + (long)h * qkv_hs;
-  const long o_off = (long)b * o_bs + (long)h * o_hs;
-  // wave's two q-blocks: rows [qA, qA+32) and [qB, qB+32)
-  const int q_baseA = qb * rows_per_wg + wid * FA_QB;
-  const int q_baseB = q_baseA + FA_QWG;
-  const int my_qA = q_baseA + col;
-  const int my_qB = q_baseB + col;
+  const FaQBlocks qb = fa_qblocks(L, wid);
+  const int b = qb.bh / H;
+  const int h = qb.bh % H;
+  const long qkv_off = (long)b * g.qkv_bs + (long)h * g.qkv_hs;
+  const long o_off = (long)b * g.o_bs + (long)h * g.o_hs;
+  const int my_qA = qb.qA + col;
+  const int my_qB = qb.qB + col;
   const bool validA = my_qA < L;
   const bool validB = my_qB < L;
   const float* mrow = mask ? mask + (long)b * L : nullptr;
 
   short8_t qfA[4], qfB[4];
   {
-    const short* qrA = q + qkv_off + (long)(validA ? my_qA : L - 1) * qkv_rs;
-    const short* qrB = q + qkv_off + (long)(validB ? my_qB : L - 1) * qkv_rs;
+    const short* qrA = q + qkv_off + (long)(validA ? my_qA : L - 1) * g.qkv_rs;
+    const short* qrB = q + qkv_off + (long)(validB ? my_qB : L - 1) * g.qkv_rs;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       qfA[c] = *(const short8_t*)(qrA + c * 16 + half * 8);
@@ -135,44 +309,34 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
     int last = fa_last_active_kv(mrow, L, tid, (int*)alpha_lds);
     if (last >= 0) n_kv_eff = min(n_kv, last / FA_KVB + 1);
   }
-  const int srow = tid >> 3, sc8 = (tid & 7) * 16;
-  short8_t kv8 = *(const short8_t*)(k + qkv_off + (long)srow * qkv_rs +
-                                    (sc8 >> 1));
-  short8_t vv8 = *(const short8_t*)(v + qkv_off + (long)srow * qkv_rs +
-                                    (sc8 >> 1));
+  const FaStager st(tid);
+  short8_t kv8 = st.load(k + qkv_off, 0, g.qkv_rs);
+  short8_t vv8 = st.load(v + qkv_off, 0, g.qkv_rs);
   for (int kt = 0; kt < n_kv_eff; ++kt) {
     const int kv0 = kt * FA_KVB;
     __syncthreads();
-    {
-      *(short8_t*)((char*)k_lds + srow * 128 + kswz(srow, sc8)) = kv8;
-      *(short8_t*)((char*)v_lds + srow * 128 + kswz(srow, sc8)) = vv8;
-    }
+    st.store(k_lds, kv8);
+    st.store(v_lds, vv8);
     __syncthreads();
     if (kt + 1 < n_kv_eff) {
-      kv8 = *(const short8_t*)(k + qkv_off +
-                               (long)(kv0 + FA_KVB + srow) * qkv_rs + (sc8 >> 1));
-      vv8 = *(const short8_t*)(v + qkv_off +
-                               (long)(kv0 + FA_KVB + srow) * qkv_rs + (sc8 >> 1));
+      kv8 = st.load(k + qkv_off, kv0 + FA_KVB, g.qkv_rs);
+      vv8 = st.load(v + qkv_off, kv0 + FA_KVB, g.qkv_rs);
     }
 
-    // mask-bias loads HOISTED above the QK chain (round 2): issued per
-    // register inside the softmax loop they sit exposed on the serial
-    // path between the mfma results and the exp chain
+    // mask-bias loads HOISTED above the QK chain: issued per register
+    // inside the softmax loop they sit exposed on the serial path between
+    // the mfma results and the exp chain
     float mb_r[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int kv_local = (r & 3) + 8 * (r >> 2) + 4 * half;
-      mb_r[r] = mrow ? mrow[kv0 + kv_local] : 0.f;
-    }
+    for (int r = 0; r < 16; ++r)
+      mb_r[r] = mrow ? mrow[kv0 + c_row(r, half)] : 0.f;
 
     // ---- QK^T for BOTH q-blocks (8 back-to-back MFMAs) ----
     f32x16 sA = (f32x16)(0.f), sB = (f32x16)(0.f);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      int byte_off = (16 * c + 8 * half) * 2;
-      short8_t kf = *(const short8_t*)((char*)k_lds + col * 128 +
-                                       kswz(col, byte_off));
+      short8_t kf = tile_row_frag(k_lds, col, half, c);
       sA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qfA[c], sA, 0, 0, 0);
       sB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qfB[c], sB, 0, 0, 0);
     }
@@ -207,12 +371,13 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
     lA = lA * aA + rsA; mA = mnA;
     lB = lB * aB + rsB; mB = mnB;
 
-    // O rescale (round 2): alpha broadcast by __shfl (v_readlane — the
-    // value for q-row r lives in lane r) instead of an LDS round-trip
-    // (was 2 stores + 64 reads/tile), and skipped wave-uniformly when no
-    // row's running max moved this tile (aA==aB==1 exactly; common once
-    // the max stabilizes a few tiles in).  Wave-local state only, so the
-    // uniform skip is race-free.
+    // O rescale: alpha for q-row r lives in lane r, but the O accumulators
+    // hold q rows by REGISTER, so each lane needs 16 other lanes' alphas.
+    // They are broadcast through the wave's own alpha_lds slice, and the
+    // whole rescale is skipped wave-uniformly when no row's running max
+    // moved this tile (aA==aB==1 exactly; common once the max stabilizes
+    // a few tiles in).  Wave-local state only, so the uniform skip is
+    // race-free.
     if (__builtin_amdgcn_ballot_w64(aA != 1.f || aB != 1.f)) {
       // LDS broadcast beat a per-register __shfl chain here (382 vs
       // ~368 us measured): 32 dependent v_readlane+mul pairs serialize
@@ -223,120 +388,62 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+          int qrow = c_row(r, half);
           oA[t][r] *= alpha_lds[wid * 64 + qrow];
           oB[t][r] *= alpha_lds[wid * 64 + 32 + qrow];
         }
       }
     }
 
-    // ---- P -> bf16 fragments, both blocks ----
+    // ---- P -> bf16 A-fragments, both blocks ----
     short8_t pfA[2], pfB[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
-      uint4_t uA, uB;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        int r0 = c * 8 + 2 * i;
-        int r1 = c * 8 + 4 + 2 * i;
-        unsigned loA, hiA, loB, hiB;
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(loA)
-            : "v"(svA[r0]), "v"(svA[r0 + 1]));
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(hiA)
-            : "v"(svA[r1]), "v"(svA[r1 + 1]));
-        auto swA = __builtin_amdgcn_permlane32_swap(loA, hiA, false, false);
-        uA[i] = swA[0]; uA[i + 2] = swA[1];
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(loB)
-            : "v"(svB[r0]), "v"(svB[r0 + 1]));
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(hiB)
-            : "v"(svB[r1]), "v"(svB[r1 + 1]));
-        auto swB = __builtin_amdgcn_permlane32_swap(loB, hiB, false, false);
-        uB[i] = swB[0]; uB[i + 2] = swB[1];
-      }
-      pfA[c] = __builtin_bit_cast(short8_t, uA);
-      pfB[c] = __builtin_bit_cast(short8_t, uB);
-    }
+    c_to_afrag2(svA, pfA, svB, pfB);
 
-    // ---- PV for both blocks from tr_b16-gathered V fragments ----
-    {
-      typedef __attribute__((ext_vector_type(2))) unsigned uint2_t;
-      const unsigned vbase = (unsigned)(unsigned long)(char*)v_lds;
-      const int kv_mate = (lane >> 2) & 3;
-      const int d_lane = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-      unsigned a[8];
+    // ---- PV for both blocks from tr_b16-gathered V^T fragments ----
+    FaTrFrags vT;
+    tr_gather(v_lds, tro, vT);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int c = 0; c < 2; ++c)
+    for (int t = 0; t < 2; ++t) {
 #pragma unroll
-        for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            int kv = 16 * c + 8 * half + 4 * rr + kv_mate;
-            int dcol = (32 * t + d_lane) * 2;
-            a[c * 4 + rr * 2 + t] =
-                vbase + kv * 128 + (dcol ^ ((kv & 7) << 4));
-          }
-      uint2_t r[8];
-      asm volatile(
-          "ds_read_b64_tr_b16 %0, %8\n\t"
-          "ds_read_b64_tr_b16 %1, %9\n\t"
-          "ds_read_b64_tr_b16 %2, %10\n\t"
-          "ds_read_b64_tr_b16 %3, %11\n\t"
-          "ds_read_b64_tr_b16 %4, %12\n\t"
-          "ds_read_b64_tr_b16 %5, %13\n\t"
-          "ds_read_b64_tr_b16 %6, %14\n\t"
-          "ds_read_b64_tr_b16 %7, %15\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]),
-            "=&v"(r[4]), "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7])
-          : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]),
-            "v"(a[6]), "v"(a[7])
-          : "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
-          uint4_t w;
-          w[0] = r[c * 4 + 0 * 2 + t][0];
-          w[1] = r[c * 4 + 0 * 2 + t][1];
-          w[2] = r[c * 4 + 1 * 2 + t][0];
-          w[3] = r[c * 4 + 1 * 2 + t][1];
-          short8_t vf = __builtin_bit_cast(short8_t, w);
-          oA[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pfA[c], vf,
-                                                          oA[t], 0, 0, 0);
-          oB[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pfB[c], vf,
-                                                          oB[t], 0, 0, 0);
-        }
+      for (int c = 0; c < 2; ++c) {
+        short8_t vf = vT.frag(c, t);
+        oA[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pfA[c], vf, oA[t],
+                                                        0, 0, 0);
+        oB[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pfB[c], vf, oB[t],
+                                                        0, 0, 0);
       }
-      __builtin_amdgcn_s_setprio(0);
     }
+    __builtin_amdgcn_s_setprio(0);
   }
 
   // ---- epilogue: both blocks ----
   if (lse != nullptr && half == 0) {
-    if (validA) lse[(long)bh * L + my_qA] = mA + __logf(lA);
-    if (validB) lse[(long)bh * L + my_qB] = mB + __logf(lB);
+    if (validA) lse[(long)qb.bh * L + my_qA] = mA + __logf(lA);
+    if (validB) lse[(long)qb.bh * L + my_qB] = mB + __logf(lB);
   }
   const float invA = 1.0f / lA, invB = 1.0f / lB;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    int rloc = (r & 3) + 8 * (r >> 2) + 4 * half;
+    int rloc = c_row(r, half);
     float iA = __shfl(invA, rloc, WAVE);
     float iB = __shfl(invB, rloc, WAVE);
-    int qA = q_baseA + rloc, qB = q_baseB + rloc;
+    int qA = qb.qA + rloc, qB = qb.qB + rloc;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       if (qA < L)
-        o[o_off + (long)qA * o_rs + 32 * t + col] =
+        o[o_off + (long)qA * g.o_rs + 32 * t + col] =
             f32_to_bf16(oA[t][r] * iA);
       if (qB < L)
-        o[o_off + (long)qB * o_rs + 32 * t + col] =
+        o[o_off + (long)qB * g.o_rs + 32 * t + col] =
             f32_to_bf16(oB[t][r] * iB);
     }
   }
+}
+
+// Grid of a kernel whose workgroup owns `rows_per_wg` rows of one (b, h).
+static dim3 fa_grid(int B, int H, int L, int rows_per_wg) {
+  return dim3(B * H * ((L + rows_per_wg - 1) / rows_per_wg));
 }
 
 extern "C" hipError_t flash_fwd_launch(const void* q, const void* k,
@@ -344,14 +451,10 @@ extern "C" hipError_t flash_fwd_launch(const void* q, const void* k,
                                        void* o, void* lse, int B, int H,
                                        int L, float scale,
                                        hipStream_t stream) {
-  int n_qblocks = (L + 2 * FA_QWG - 1) / (2 * FA_QWG);
-  dim3 grid(B * H * n_qblocks);
-  size_t shm = K_LDS_BYTES + VT_LDS_BYTES + FA_WAVES * 64 * sizeof(float);
-  flash_fwd_kernel<<<grid, FA_BLOCK, shm, stream>>>(
+  flash_fwd_kernel<<<fa_grid(B, H, L, FA_Q2WG), FA_BLOCK, FWD_LDS_BYTES,
+                     stream>>>(
       (const short*)q, (const short*)k, (const short*)v, (const float*)mask,
-      (short*)o, (float*)lse, B, H, L, scale,
-      (long)H * L * FA_DH, (long)L * FA_DH, FA_DH,
-      (long)H * L * FA_DH, (long)L * FA_DH, FA_DH);
+      (short*)o, (float*)lse, B, H, L, scale, FaGeom::bhld(H, L));
   return hipGetLastError();
 }
 
@@ -362,21 +465,17 @@ extern "C" hipError_t flash_fwd_packed_launch(const void* qkv,
                                               float scale,
                                               hipStream_t stream) {
   const int D = H * FA_DH;
-  int n_qblocks = (L + 2 * FA_QWG - 1) / (2 * FA_QWG);
-  dim3 grid(B * H * n_qblocks);
-  size_t shm = K_LDS_BYTES + VT_LDS_BYTES + FA_WAVES * 64 * sizeof(float);
-  flash_fwd_kernel<<<grid, FA_BLOCK, shm, stream>>>(
+  flash_fwd_kernel<<<fa_grid(B, H, L, FA_Q2WG), FA_BLOCK, FWD_LDS_BYTES,
+                     stream>>>(
       (const short*)qkv, (const short*)qkv + D, (const short*)qkv + 2 * D,
       (const float*)mask, (short*)o, (float*)lse, B, H, L, scale,
-      (long)L * 3 * D, 64L, 3 * D,
-      (long)L * D, 64L, D);
+      FaGeom::packed(H, L));
   return hipGetLastError();
 }
 
-
-
 // ---------------------------------------------------------------------------
-// Flash backward: ONE kernel recomputes P/dS and produces dS, dK and dV.
+// Flash backward, dK/dV half: ONE kernel recomputes P and dS and
+// accumulates dK and dV in registers.
 //
 //   P[q, kv]  = exp(scale * S + mask_bias[kv] - lse[q])
 //   dP[q, kv] = dO @ V^T
@@ -389,14 +488,16 @@ extern "C" hipError_t flash_fwd_packed_launch(const void* qkv,
 // waves share LDS-staged Q/dO tiles (32 q rows per tile).  Per tile the
 // wave computes S and dP in the (reg=q, lane=kv) orientation — so lse/ddot
 // index by register and the mask bias is one scalar per lane — then
-// repacks P and dS into A-fragments (cvt_pk_bf16 + permlane32_swap, which
-// maps C-layout (reg=R, lane=C) to fragment [row=C][k=R]) and feeds two
-// MFMA accumulation chains against dO^T / Q^T fragments gathered with
-// ds_read_b64_tr_b16 from the already-staged tiles.  dS leaves in the
-// natural [B, H, L_q, L_kv] layout so the remaining gradient is ONE
-// non-transposed library bmm: dQ = dS @ K.  This replaces the previous
-// P^T/dS^T materialization + three batched bmms (the [512,512,64]-shaped
-// batched bmms ran at ~107 TF in hipBLASLt — see profiles/).
+// repacks P and dS into A-fragments [row=kv][k=q] and feeds two MFMA
+// accumulation chains against dO^T / Q^T fragments gathered from the
+// already-staged tiles.  Keeping the whole contraction in one kernel avoids
+// the [512,512,64]-shaped batched bmms, which ran at ~107 TF in hipBLASLt
+// (see profiles/).
+//
+// dQ is not produced here: by default it comes from
+// flash_dq_recompute_kernel.  With ds != nullptr the kernel additionally
+// writes dS in the natural [B, H, L_q, L_kv] layout for flash_dq_kernel
+// (the A/B path kept for comparison and tests).
 //
 // Mirrors reference capability only in spirit: the reference ships no
 // attention kernels (data-only replication package).
@@ -410,20 +511,19 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
                        const float* __restrict__ ddot,
                        short* __restrict__ ds, short* __restrict__ dk,
                        short* __restrict__ dv,
-                       int B, int H, int L, float scale,
-                       long qkv_bs, long qkv_hs, int qkv_rs,
-                       long o_bs, long o_hs, int o_rs) {
+                       int B, int H, int L, float scale, FaGeom g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  short* q_lds = (short*)smem;                        // swizzled [32][64]
-  short* do_lds = (short*)(smem + K_LDS_BYTES);       // swizzled [32][64]
-  float* lse_lds = (float*)(smem + 2 * K_LDS_BYTES);  // [32]
-  float* dd_lds = lse_lds + 32;                       // [32]
+  short* q_lds = (short*)smem;
+  short* do_lds = (short*)(smem + TILE_LDS_BYTES);
+  float* lse_lds = (float*)(smem + 2 * TILE_LDS_BYTES);  // [32]
+  float* dd_lds = lse_lds + 32;                          // [32]
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wid = tid / WAVE;
   const int col = lane & 31;
   const int half = lane >> 5;
+  const FaTrOffsets tro = tr_offsets(lane, half);
 
   const int n_kvblocks = (L + FA_QWG - 1) / FA_QWG;   // 128 kv rows per WG
   int bid = xcd_group_remap(blockIdx.x, gridDim.x, n_kvblocks);
@@ -431,8 +531,8 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   int kb = bid % n_kvblocks;
   const int b = bh / H;
   const int h = bh % H;
-  const long qkv_off = (long)b * qkv_bs + (long)h * qkv_hs;
-  const long o_off = (long)b * o_bs + (long)h * o_hs;
+  const long qkv_off = (long)b * g.qkv_bs + (long)h * g.qkv_hs;
+  const long o_off = (long)b * g.o_bs + (long)h * g.o_hs;
   const long bh_sq = (long)bh * L * L;
   const int kv_base = kb * FA_QWG + wid * FA_KVB;     // this wave's 32 kv rows
   const int my_kv = kv_base + col;
@@ -440,7 +540,7 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   const float* mrow = mask ? mask + (long)b * L : nullptr;
   const float mb = mrow ? mrow[min(my_kv, L - 1)] : 0.f;
 
-  // Early-out (round 2): if every kv row this workgroup owns is padding
+  // Early-out: if every kv row this workgroup owns is padding
   // (bias <= -1e8) and the sequence has at least one real token, P and dS
   // are exactly +0.0f for every q — dK/dV are zero and the whole q loop is
   // skipped (the epilogue writes the zero accumulators).  Requires
@@ -471,8 +571,8 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   // K and V fragments for this wave's kv block (resident all kernel)
   short8_t kf[4], vf[4];
   if (!skip_tile) {
-    const short* kr = k + qkv_off + (long)(kv_valid ? my_kv : L - 1) * qkv_rs;
-    const short* vr = v + qkv_off + (long)(kv_valid ? my_kv : L - 1) * qkv_rs;
+    const short* kr = k + qkv_off + (long)(kv_valid ? my_kv : L - 1) * g.qkv_rs;
+    const short* vr = v + qkv_off + (long)(kv_valid ? my_kv : L - 1) * g.qkv_rs;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       kf[c] = *(const short8_t*)(kr + c * 16 + half * 8);
@@ -487,28 +587,22 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   }
   if (!skip_tile) {
   const int n_q = L / 32;
-  const int srow = tid >> 3, sc8 = (tid & 7) * 16;
-  short8_t qv8 = *(const short8_t*)(q + qkv_off + (long)srow * qkv_rs +
-                                    (sc8 >> 1));
-  short8_t dv8 = *(const short8_t*)(dout + o_off + (long)srow * o_rs +
-                                    (sc8 >> 1));
+  const FaStager st(tid);
+  short8_t qv8 = st.load(q + qkv_off, 0, g.qkv_rs);
+  short8_t dv8 = st.load(dout + o_off, 0, g.o_rs);
   for (int qt = 0; qt < n_q; ++qt) {
     const int q0 = qt * 32;
     __syncthreads();
-    {
-      *(short8_t*)((char*)q_lds + srow * 128 + kswz(srow, sc8)) = qv8;
-      *(short8_t*)((char*)do_lds + srow * 128 + kswz(srow, sc8)) = dv8;
-      if (tid < 32) {
-        lse_lds[tid] = lse[(long)bh * L + q0 + tid];
-        dd_lds[tid] = ddot[(long)bh * L + q0 + tid];
-      }
+    st.store(q_lds, qv8);
+    st.store(do_lds, dv8);
+    if (tid < 32) {
+      lse_lds[tid] = lse[(long)bh * L + q0 + tid];
+      dd_lds[tid] = ddot[(long)bh * L + q0 + tid];
     }
     __syncthreads();
     if (qt + 1 < n_q) {
-      qv8 = *(const short8_t*)(q + qkv_off + (long)(q0 + 32 + srow) * qkv_rs +
-                               (sc8 >> 1));
-      dv8 = *(const short8_t*)(dout + o_off + (long)(q0 + 32 + srow) * o_rs +
-                               (sc8 >> 1));
+      qv8 = st.load(q + qkv_off, q0 + 32, g.qkv_rs);
+      dv8 = st.load(dout + o_off, q0 + 32, g.o_rs);
     }
 
     if (wave_skip) continue;
@@ -518,11 +612,8 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      int byte_off = (16 * c + 8 * half) * 2;
-      short8_t qfrag = *(const short8_t*)((char*)q_lds + col * 128 +
-                                          kswz(col, byte_off));
-      short8_t dofrag = *(const short8_t*)((char*)do_lds + col * 128 +
-                                           kswz(col, byte_off));
+      short8_t qfrag = tile_row_frag(q_lds, col, half, c);
+      short8_t dofrag = tile_row_frag(do_lds, col, half, c);
       s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfrag, kf[c], s_acc,
                                                       0, 0, 0);
       dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dofrag, vf[c], dp_acc,
@@ -534,129 +625,40 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
     float pv[16], gv[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      int ql = (r & 3) + 8 * (r >> 2) + 4 * half;
+      int ql = c_row(r, half);
       pv[r] = __expf(s_acc[r] * scale + mb - lse_lds[ql]);
       gv[r] = scale * pv[r] * (dp_acc[r] - dd_lds[ql]);
     }
     // dS out, natural [q, kv] rows (2 B per lane, lanes contiguous in kv);
-    // skipped entirely when ds == nullptr (round 2: dQ is recomputed by
-    // flash_dq_recompute_kernel, no dS materialization)
+    // only on the A/B path that feeds flash_dq_kernel
     if (ds != nullptr && kv_valid) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int ql = (r & 3) + 8 * (r >> 2) + 4 * half;
-        ds[bh_sq + (long)(q0 + ql) * L + my_kv] = f32_to_bf16(gv[r]);
-      }
+      for (int r = 0; r < 16; ++r)
+        ds[bh_sq + (long)(q0 + c_row(r, half)) * L + my_kv] =
+            f32_to_bf16(gv[r]);
     }
 
     // repack P and dS to A-fragments [row=kv][k=q]
     short8_t pf[2], gf[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
-      uint4_t up, ug;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        int r0 = c * 8 + 2 * i;
-        int r1 = c * 8 + 4 + 2 * i;
-        unsigned lo, hi;
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(lo)
-            : "v"(pv[r0]), "v"(pv[r0 + 1]));
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(hi)
-            : "v"(pv[r1]), "v"(pv[r1 + 1]));
-        auto sw = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
-        up[i] = sw[0]; up[i + 2] = sw[1];
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(lo)
-            : "v"(gv[r0]), "v"(gv[r0 + 1]));
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(hi)
-            : "v"(gv[r1]), "v"(gv[r1 + 1]));
-        auto sw2 = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
-        ug[i] = sw2[0]; ug[i + 2] = sw2[1];
-      }
-      pf[c] = __builtin_bit_cast(short8_t, up);
-      gf[c] = __builtin_bit_cast(short8_t, ug);
-    }
+    c_to_afrag2(pv, pf, gv, gf);
 
-    // dO^T and Q^T B-fragments [row=d][k=q] via lane-grid transpose reads,
-    // then the two accumulation chains (reg=kv rows, lane=d cols)
-    {
-      typedef __attribute__((ext_vector_type(2))) unsigned uint2_t;
-      const unsigned dobase = (unsigned)(unsigned long)(char*)do_lds;
-      const unsigned qbase = (unsigned)(unsigned long)(char*)q_lds;
-      const int q_mate = (lane >> 2) & 3;
-      const int d_lane = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-      unsigned ad[8], aq[8];
+    // dO^T and Q^T B-fragments [row=d][k=q], then the two accumulation
+    // chains (reg=kv rows, lane=d cols)
+    FaTrFrags doT, qT;
+    tr_issue(do_lds, tro, doT);
+    tr_gather(q_lds, tro, qT);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int c = 0; c < 2; ++c)
+    for (int t = 0; t < 2; ++t) {
 #pragma unroll
-        for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            int qq = 16 * c + 8 * half + 4 * rr + q_mate;
-            int dcol = (32 * t + d_lane) * 2;
-            int off = qq * 128 + (dcol ^ ((qq & 7) << 4));
-            ad[c * 4 + rr * 2 + t] = dobase + off;
-            aq[c * 4 + rr * 2 + t] = qbase + off;
-          }
-      uint2_t rd[8], rq[8];
-      asm volatile(
-          "ds_read_b64_tr_b16 %0, %8\n\t"
-          "ds_read_b64_tr_b16 %1, %9\n\t"
-          "ds_read_b64_tr_b16 %2, %10\n\t"
-          "ds_read_b64_tr_b16 %3, %11\n\t"
-          "ds_read_b64_tr_b16 %4, %12\n\t"
-          "ds_read_b64_tr_b16 %5, %13\n\t"
-          "ds_read_b64_tr_b16 %6, %14\n\t"
-          "ds_read_b64_tr_b16 %7, %15\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(rd[0]), "=&v"(rd[1]), "=&v"(rd[2]), "=&v"(rd[3]),
-            "=&v"(rd[4]), "=&v"(rd[5]), "=&v"(rd[6]), "=&v"(rd[7])
-          : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "v"(ad[4]),
-            "v"(ad[5]), "v"(ad[6]), "v"(ad[7])
-          : "memory");
-      asm volatile(
-          "ds_read_b64_tr_b16 %0, %8\n\t"
-          "ds_read_b64_tr_b16 %1, %9\n\t"
-          "ds_read_b64_tr_b16 %2, %10\n\t"
-          "ds_read_b64_tr_b16 %3, %11\n\t"
-          "ds_read_b64_tr_b16 %4, %12\n\t"
-          "ds_read_b64_tr_b16 %5, %13\n\t"
-          "ds_read_b64_tr_b16 %6, %14\n\t"
-          "ds_read_b64_tr_b16 %7, %15\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(rq[0]), "=&v"(rq[1]), "=&v"(rq[2]), "=&v"(rq[3]),
-            "=&v"(rq[4]), "=&v"(rq[5]), "=&v"(rq[6]), "=&v"(rq[7])
-          : "v"(aq[0]), "v"(aq[1]), "v"(aq[2]), "v"(aq[3]), "v"(aq[4]),
-            "v"(aq[5]), "v"(aq[6]), "v"(aq[7])
-          : "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
-          uint4_t wd, wq;
-          wd[0] = rd[c * 4 + 0 * 2 + t][0];
-          wd[1] = rd[c * 4 + 0 * 2 + t][1];
-          wd[2] = rd[c * 4 + 1 * 2 + t][0];
-          wd[3] = rd[c * 4 + 1 * 2 + t][1];
-          wq[0] = rq[c * 4 + 0 * 2 + t][0];
-          wq[1] = rq[c * 4 + 0 * 2 + t][1];
-          wq[2] = rq[c * 4 + 1 * 2 + t][0];
-          wq[3] = rq[c * 4 + 1 * 2 + t][1];
-          short8_t dof = __builtin_bit_cast(short8_t, wd);
-          short8_t qf = __builtin_bit_cast(short8_t, wq);
-          dv_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf[c], dof,
-                                                              dv_acc[t],
-                                                              0, 0, 0);
-          dk_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gf[c], qf,
-                                                              dk_acc[t],
-                                                              0, 0, 0);
-        }
+      for (int c = 0; c < 2; ++c) {
+        dv_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            pf[c], doT.frag(c, t), dv_acc[t], 0, 0, 0);
+        dk_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            gf[c], qT.frag(c, t), dk_acc[t], 0, 0, 0);
       }
-      __builtin_amdgcn_s_setprio(0);
     }
+    __builtin_amdgcn_s_setprio(0);
   }
   }   // !skip_tile
 
@@ -665,9 +667,9 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   for (int t = 0; t < 2; ++t) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      int kvl = (r & 3) + 8 * (r >> 2) + 4 * half;
+      int kvl = c_row(r, half);
       if (kv_base + kvl >= L) continue;
-      long off = qkv_off + (long)(kv_base + kvl) * qkv_rs + 32 * t + col;
+      long off = qkv_off + (long)(kv_base + kvl) * g.qkv_rs + 32 * t + col;
       dv[off] = f32_to_bf16(dv_acc[t][r]);
       dk[off] = f32_to_bf16(dk_acc[t][r]);
     }
@@ -678,15 +680,11 @@ extern "C" hipError_t flash_bwd_fused_launch(
     const void* q, const void* k, const void* v, const void* dout,
     const void* mask, const void* lse, const void* ddot, void* ds, void* dk,
     void* dv, int B, int H, int L, float scale, hipStream_t stream) {
-  int n_kvblocks = (L + FA_QWG - 1) / FA_QWG;
-  dim3 grid(B * H * n_kvblocks);
-  size_t shm = 2 * K_LDS_BYTES + 64 * sizeof(float);
-  flash_bwd_fused_kernel<<<grid, FA_BLOCK, shm, stream>>>(
+  flash_bwd_fused_kernel<<<fa_grid(B, H, L, FA_QWG), FA_BLOCK, BWD_LDS_BYTES,
+                           stream>>>(
       (const short*)q, (const short*)k, (const short*)v, (const short*)dout,
       (const float*)mask, (const float*)lse, (const float*)ddot, (short*)ds,
-      (short*)dk, (short*)dv, B, H, L, scale,
-      (long)H * L * FA_DH, (long)L * FA_DH, FA_DH,
-      (long)H * L * FA_DH, (long)L * FA_DH, FA_DH);
+      (short*)dk, (short*)dv, B, H, L, scale, FaGeom::bhld(H, L));
   return hipGetLastError();
 }
 
@@ -696,50 +694,40 @@ extern "C" hipError_t flash_bwd_fused_packed_launch(
     const void* ddot, void* dqkv, int B, int H, int L, float scale,
     hipStream_t stream) {
   const int D = H * FA_DH;
-  int n_kvblocks = (L + FA_QWG - 1) / FA_QWG;
-  dim3 grid(B * H * n_kvblocks);
-  size_t shm = 2 * K_LDS_BYTES + 64 * sizeof(float);
-  flash_bwd_fused_kernel<<<grid, FA_BLOCK, shm, stream>>>(
+  flash_bwd_fused_kernel<<<fa_grid(B, H, L, FA_QWG), FA_BLOCK, BWD_LDS_BYTES,
+                           stream>>>(
       (const short*)qkv, (const short*)qkv + D, (const short*)qkv + 2 * D,
       (const short*)dout, (const float*)mask, (const float*)lse,
       (const float*)ddot, nullptr,
       (short*)dqkv + D, (short*)dqkv + 2 * D, B, H, L, scale,
-      (long)L * 3 * D, 64L, 3 * D,
-      (long)L * D, 64L, D);
+      FaGeom::packed(H, L));
   return hipGetLastError();
 }
 
-
-
-// dQ = dS @ K — the final attention gradient, as a purpose-built kernel
-// instead of a library bmm ([L, L] x [L, 64] batched shapes run at ~225 TF
-// in hipBLASLt).  Structure mirrors flash_fwd's PV stage: two independent
+// dQ = dS @ K from a materialized dS — a purpose-built kernel instead of a
+// library bmm ([L, L] x [L, 64] batched shapes run at ~225 TF in
+// hipBLASLt).  Structure mirrors flash_fwd's PV stage: two independent
 // 32-row q-blocks per wave (ILP), dS rows read straight from HBM as MFMA
 // A-fragments (contiguous short8 per lane), K tiles staged swizzled in LDS
-// and gathered as K^T B-fragments with ds_read_b64_tr_b16.
+// and gathered as K^T B-fragments.  ds/k/dq are [B, H, L, *] contiguous.
 extern "C" __global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_dq_kernel(const short* __restrict__ ds, const short* __restrict__ k,
                 short* __restrict__ dq, int B, int H, int L) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  short* k_lds = (short*)smem;                       // swizzled [32][64]
+  short* k_lds = (short*)smem;
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wid = tid / WAVE;
   const int col = lane & 31;
   const int half = lane >> 5;
+  const FaTrOffsets tro = tr_offsets(lane, half);
 
-  const int rows_per_wg = 2 * FA_QWG;                 // 256 q rows
-  const int n_qblocks = (L + rows_per_wg - 1) / rows_per_wg;
-  int bid = xcd_group_remap(blockIdx.x, gridDim.x, n_qblocks);
-  int bh = bid / n_qblocks;
-  int qb = bid % n_qblocks;
-  const long bh_off = (long)bh * L * FA_DH;
-  const long bh_sq = (long)bh * L * L;
-  const int q_baseA = qb * rows_per_wg + wid * FA_QB;
-  const int q_baseB = q_baseA + FA_QWG;
-  const int my_qA = min(q_baseA + col, L - 1);
-  const int my_qB = min(q_baseB + col, L - 1);
+  const FaQBlocks qb = fa_qblocks(L, wid);
+  const long bh_off = (long)qb.bh * L * FA_DH;
+  const long bh_sq = (long)qb.bh * L * L;
+  const int my_qA = min(qb.qA + col, L - 1);
+  const int my_qB = min(qb.qB + col, L - 1);
   const short* dsA_row = ds + bh_sq + (long)my_qA * L;
   const short* dsB_row = ds + bh_sq + (long)my_qB * L;
 
@@ -748,18 +736,14 @@ flash_dq_kernel(const short* __restrict__ ds, const short* __restrict__ k,
   for (int t = 0; t < 2; ++t) { oA[t] = (f32x16)(0.f); oB[t] = (f32x16)(0.f); }
 
   const int n_kv = L / FA_KVB;
-  const int srow = tid >> 3, sc8 = (tid & 7) * 16;
-  short8_t kv8 = *(const short8_t*)(k + bh_off + (long)srow * FA_DH +
-                                    (sc8 >> 1));
+  const FaStager st(tid);
+  short8_t kv8 = st.load(k + bh_off, 0, FA_DH);
   for (int kt = 0; kt < n_kv; ++kt) {
     const int kv0 = kt * FA_KVB;
     __syncthreads();
-    *(short8_t*)((char*)k_lds + srow * 128 + kswz(srow, sc8)) = kv8;
+    st.store(k_lds, kv8);
     __syncthreads();
-    if (kt + 1 < n_kv)
-      kv8 = *(const short8_t*)(k + bh_off +
-                               (long)(kv0 + FA_KVB + srow) * FA_DH +
-                               (sc8 >> 1));
+    if (kt + 1 < n_kv) kv8 = st.load(k + bh_off, kv0 + FA_KVB, FA_DH);
     // dS A-fragments straight from HBM: lane reads its q row's kv chunk
     short8_t aA[2], aB[2];
 #pragma unroll
@@ -767,51 +751,14 @@ flash_dq_kernel(const short* __restrict__ ds, const short* __restrict__ k,
       aA[c] = *(const short8_t*)(dsA_row + kv0 + 16 * c + 8 * half);
       aB[c] = *(const short8_t*)(dsB_row + kv0 + 16 * c + 8 * half);
     }
-    // K^T B-fragments via lane-grid transpose reads (same law as fwd V)
-    typedef __attribute__((ext_vector_type(2))) unsigned uint2_t;
-    const unsigned kbase = (unsigned)(unsigned long)(char*)k_lds;
-    const int kv_mate = (lane >> 2) & 3;
-    const int d_lane = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-    unsigned a[8];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          int kv = 16 * c + 8 * half + 4 * rr + kv_mate;
-          int dcol = (32 * t + d_lane) * 2;
-          a[c * 4 + rr * 2 + t] = kbase + kv * 128 + (dcol ^ ((kv & 7) << 4));
-        }
-    uint2_t r[8];
-    asm volatile(
-        "ds_read_b64_tr_b16 %0, %8\n\t"
-        "ds_read_b64_tr_b16 %1, %9\n\t"
-        "ds_read_b64_tr_b16 %2, %10\n\t"
-        "ds_read_b64_tr_b16 %3, %11\n\t"
-        "ds_read_b64_tr_b16 %4, %12\n\t"
-        "ds_read_b64_tr_b16 %5, %13\n\t"
-        "ds_read_b64_tr_b16 %6, %14\n\t"
-        "ds_read_b64_tr_b16 %7, %15\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4]),
-          "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7])
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]),
-          "v"(a[6]), "v"(a[7])
-        : "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    FaTrFrags kT;
+    tr_gather(k_lds, tro, kT);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
-        uint4_t w;
-        w[0] = r[c * 4 + 0 * 2 + t][0];
-        w[1] = r[c * 4 + 0 * 2 + t][1];
-        w[2] = r[c * 4 + 1 * 2 + t][0];
-        w[3] = r[c * 4 + 1 * 2 + t][1];
-        short8_t kf = __builtin_bit_cast(short8_t, w);
+        short8_t kf = kT.frag(c, t);
         oA[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aA[c], kf, oA[t],
                                                         0, 0, 0);
         oB[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aB[c], kf, oB[t],
@@ -825,8 +772,8 @@ flash_dq_kernel(const short* __restrict__ ds, const short* __restrict__ k,
   for (int t = 0; t < 2; ++t) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      int rloc = (r & 3) + 8 * (r >> 2) + 4 * half;
-      int qA = q_baseA + rloc, qB = q_baseB + rloc;
+      int rloc = c_row(r, half);
+      int qA = qb.qA + rloc, qB = qb.qB + rloc;
       if (qA < L)
         dq[bh_off + (long)qA * FA_DH + 32 * t + col] = f32_to_bf16(oA[t][r]);
       if (qB < L)
@@ -838,20 +785,19 @@ flash_dq_kernel(const short* __restrict__ ds, const short* __restrict__ k,
 extern "C" hipError_t flash_dq_launch(const void* ds, const void* k, void* dq,
                                       int B, int H, int L,
                                       hipStream_t stream) {
-  int n_qblocks = (L + 2 * FA_QWG - 1) / (2 * FA_QWG);
-  dim3 grid(B * H * n_qblocks);
-  flash_dq_kernel<<<grid, FA_BLOCK, K_LDS_BYTES, stream>>>(
+  flash_dq_kernel<<<fa_grid(B, H, L, FA_Q2WG), FA_BLOCK, DQ_LDS_BYTES,
+                    stream>>>(
       (const short*)ds, (const short*)k, (short*)dq, B, H, L);
   return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
-// dQ by recompute (round 2): forward-orientation kernel that recomputes
-// S = QK^T and dP = dO V^T per kv tile, forms dS in registers and
-// accumulates dQ = dS @ K — no dS materialization at all.  Replaces the
-// bwd pipeline's [B, H, L, L] bf16 dS HBM round-trip (1.07 GB written by
-// flash_bwd_fused + 1.07 GB re-read by flash_dq at the bench shape) and
-// the separate flash_dq pass; flash_bwd_fused now only emits dK/dV.
+// dQ by recompute: forward-orientation kernel that recomputes S = QK^T and
+// dP = dO V^T per kv tile, forms dS in registers and accumulates
+// dQ = dS @ K — no dS materialization at all.  Against the
+// flash_bwd_fused(emit dS) + flash_dq pair this saves the [B, H, L, L]
+// bf16 dS HBM round-trip (1.07 GB written + 1.07 GB re-read at the bench
+// shape).
 //
 // Structure mirrors flash_fwd exactly (two independent 32-row q-blocks per
 // wave for ILP; K/V tiles staged swizzled in LDS, double-staged across the
@@ -861,10 +807,8 @@ extern "C" hipError_t flash_dq_launch(const void* ds, const void* k, void* dq,
 //   lse/ddot are LANE-local scalars (one q row per lane), the mask bias
 //   indexes by the kv REGISTER — both orientations line up for free
 //   dS = scale * P * (dP - D) in registers
-//   dS -> A-fragments [row=q][k=kv] via the same cvt_pk_bf16 +
-//   permlane32_swap repack the fwd uses for P
-//   dQ[q, d] += mfma(dS-frag, K^T-frag), K^T gathered ds_read_b64_tr_b16
-//   from the staged K tile (same law as the fwd V^T gather).
+//   dS -> A-fragments [row=q][k=kv]
+//   dQ[q, d] += mfma(dS-frag, K^T-frag), K^T gathered from the staged K tile
 extern "C" __global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_dq_recompute_kernel(const short* __restrict__ q,
                           const short* __restrict__ k,
@@ -874,42 +818,36 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
                           const float* __restrict__ lse,
                           const float* __restrict__ ddot,
                           short* __restrict__ dq,
-                          int B, int H, int L, float scale,
-                          long qkv_bs, long qkv_hs, int qkv_rs,
-                          long o_bs, long o_hs, int o_rs) {
+                          int B, int H, int L, float scale, FaGeom g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  short* k_lds = (short*)smem;                       // swizzled [32][64]
-  short* v_lds = (short*)(smem + K_LDS_BYTES);       // swizzled [32][64]
+  short* k_lds = (short*)smem;
+  short* v_lds = (short*)(smem + TILE_LDS_BYTES);
+  int* skip_scratch = (int*)(smem + 2 * TILE_LDS_BYTES);
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wid = tid / WAVE;
   const int col = lane & 31;
   const int half = lane >> 5;
+  const FaTrOffsets tro = tr_offsets(lane, half);
 
-  const int rows_per_wg = 2 * FA_QWG;                 // 256 q rows
-  const int n_qblocks = (L + rows_per_wg - 1) / rows_per_wg;
-  int bid = xcd_group_remap(blockIdx.x, gridDim.x, n_qblocks);
-  int bh = bid / n_qblocks;
-  int qb = bid % n_qblocks;
-  const int b = bh / H;
-  const int h = bh % H;
-  const long qkv_off = (long)b * qkv_bs + (long)h * qkv_hs;
-  const long o_off = (long)b * o_bs + (long)h * o_hs;
-  const int q_baseA = qb * rows_per_wg + wid * FA_QB;
-  const int q_baseB = q_baseA + FA_QWG;
-  const int my_qA = q_baseA + col;
-  const int my_qB = q_baseB + col;
+  const FaQBlocks qb = fa_qblocks(L, wid);
+  const int b = qb.bh / H;
+  const int h = qb.bh % H;
+  const long qkv_off = (long)b * g.qkv_bs + (long)h * g.qkv_hs;
+  const long o_off = (long)b * g.o_bs + (long)h * g.o_hs;
+  const int my_qA = qb.qA + col;
+  const int my_qB = qb.qB + col;
   const bool validA = my_qA < L;
   const bool validB = my_qB < L;
   const float* mrow = mask ? mask + (long)b * L : nullptr;
 
   short8_t qfA[4], qfB[4], dofA[4], dofB[4];
   {
-    const short* qrA = q + qkv_off + (long)(validA ? my_qA : L - 1) * qkv_rs;
-    const short* qrB = q + qkv_off + (long)(validB ? my_qB : L - 1) * qkv_rs;
-    const short* drA = dout + o_off + (long)(validA ? my_qA : L - 1) * o_rs;
-    const short* drB = dout + o_off + (long)(validB ? my_qB : L - 1) * o_rs;
+    const short* qrA = q + qkv_off + (long)(validA ? my_qA : L - 1) * g.qkv_rs;
+    const short* qrB = q + qkv_off + (long)(validB ? my_qB : L - 1) * g.qkv_rs;
+    const short* drA = dout + o_off + (long)(validA ? my_qA : L - 1) * g.o_rs;
+    const short* drB = dout + o_off + (long)(validB ? my_qB : L - 1) * g.o_rs;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       qfA[c] = *(const short8_t*)(qrA + c * 16 + half * 8);
@@ -918,10 +856,10 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
       dofB[c] = *(const short8_t*)(drB + c * 16 + half * 8);
     }
   }
-  const float lseA = lse[(long)bh * L + (validA ? my_qA : L - 1)];
-  const float lseB = lse[(long)bh * L + (validB ? my_qB : L - 1)];
-  const float ddA = ddot[(long)bh * L + (validA ? my_qA : L - 1)];
-  const float ddB = ddot[(long)bh * L + (validB ? my_qB : L - 1)];
+  const float lseA = lse[(long)qb.bh * L + (validA ? my_qA : L - 1)];
+  const float lseB = lse[(long)qb.bh * L + (validB ? my_qB : L - 1)];
+  const float ddA = ddot[(long)qb.bh * L + (validA ? my_qA : L - 1)];
+  const float ddB = ddot[(long)qb.bh * L + (validB ? my_qB : L - 1)];
 
   f32x16 dqA[2], dqB[2];
 #pragma unroll
@@ -930,35 +868,27 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   const int n_kv = L / FA_KVB;
   int n_kv_eff = n_kv;
   if (mrow) {
-    int last = fa_last_active_kv(mrow, L, tid, (int*)(smem + K_LDS_BYTES + VT_LDS_BYTES));
+    int last = fa_last_active_kv(mrow, L, tid, skip_scratch);
     if (last >= 0) n_kv_eff = min(n_kv, last / FA_KVB + 1);
   }
-  const int srow = tid >> 3, sc8 = (tid & 7) * 16;
-  short8_t kv8 = *(const short8_t*)(k + qkv_off + (long)srow * qkv_rs +
-                                    (sc8 >> 1));
-  short8_t vv8 = *(const short8_t*)(v + qkv_off + (long)srow * qkv_rs +
-                                    (sc8 >> 1));
+  const FaStager st(tid);
+  short8_t kv8 = st.load(k + qkv_off, 0, g.qkv_rs);
+  short8_t vv8 = st.load(v + qkv_off, 0, g.qkv_rs);
   for (int kt = 0; kt < n_kv_eff; ++kt) {
     const int kv0 = kt * FA_KVB;
     __syncthreads();
-    {
-      *(short8_t*)((char*)k_lds + srow * 128 + kswz(srow, sc8)) = kv8;
-      *(short8_t*)((char*)v_lds + srow * 128 + kswz(srow, sc8)) = vv8;
-    }
+    st.store(k_lds, kv8);
+    st.store(v_lds, vv8);
     __syncthreads();
     if (kt + 1 < n_kv_eff) {
-      kv8 = *(const short8_t*)(k + qkv_off +
-                               (long)(kv0 + FA_KVB + srow) * qkv_rs + (sc8 >> 1));
-      vv8 = *(const short8_t*)(v + qkv_off +
-                               (long)(kv0 + FA_KVB + srow) * qkv_rs + (sc8 >> 1));
+      kv8 = st.load(k + qkv_off, kv0 + FA_KVB, g.qkv_rs);
+      vv8 = st.load(v + qkv_off, kv0 + FA_KVB, g.qkv_rs);
     }
 
     float mb_r[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int kv_local = (r & 3) + 8 * (r >> 2) + 4 * half;
-      mb_r[r] = mrow ? mrow[kv0 + kv_local] : 0.f;
-    }
+    for (int r = 0; r < 16; ++r)
+      mb_r[r] = mrow ? mrow[kv0 + c_row(r, half)] : 0.f;
 
     // ---- S and dP for BOTH q-blocks (16 back-to-back MFMAs) ----
     f32x16 sA = (f32x16)(0.f), sB = (f32x16)(0.f);
@@ -966,11 +896,8 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      int byte_off = (16 * c + 8 * half) * 2;
-      short8_t kf = *(const short8_t*)((char*)k_lds + col * 128 +
-                                       kswz(col, byte_off));
-      short8_t vf = *(const short8_t*)((char*)v_lds + col * 128 +
-                                       kswz(col, byte_off));
+      short8_t kf = tile_row_frag(k_lds, col, half, c);
+      short8_t vf = tile_row_frag(v_lds, col, half, c);
       sA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qfA[c], sA, 0, 0, 0);
       sB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qfB[c], sB, 0, 0, 0);
       pA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dofA[c], pA, 0, 0, 0);
@@ -988,89 +915,26 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
       gB[r] = scale * expB * (pB[r] - ddB);
     }
 
-    // ---- dS -> A-fragments [row=q][k=kv] (fwd P-repack idiom) ----
+    // ---- dS -> A-fragments [row=q][k=kv] ----
     short8_t gfA[2], gfB[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
-      uint4_t uA, uB;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        int r0 = c * 8 + 2 * i;
-        int r1 = c * 8 + 4 + 2 * i;
-        unsigned loA, hiA, loB, hiB;
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(loA)
-            : "v"(gA[r0]), "v"(gA[r0 + 1]));
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(hiA)
-            : "v"(gA[r1]), "v"(gA[r1 + 1]));
-        auto swA = __builtin_amdgcn_permlane32_swap(loA, hiA, false, false);
-        uA[i] = swA[0]; uA[i + 2] = swA[1];
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(loB)
-            : "v"(gB[r0]), "v"(gB[r0 + 1]));
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(hiB)
-            : "v"(gB[r1]), "v"(gB[r1 + 1]));
-        auto swB = __builtin_amdgcn_permlane32_swap(loB, hiB, false, false);
-        uB[i] = swB[0]; uB[i + 2] = swB[1];
-      }
-      gfA[c] = __builtin_bit_cast(short8_t, uA);
-      gfB[c] = __builtin_bit_cast(short8_t, uB);
-    }
+    c_to_afrag2(gA, gfA, gB, gfB);
 
     // ---- dQ += dS @ K via tr_b16-gathered K^T fragments ----
-    {
-      typedef __attribute__((ext_vector_type(2))) unsigned uint2_t;
-      const unsigned kbase = (unsigned)(unsigned long)(char*)k_lds;
-      const int kv_mate = (lane >> 2) & 3;
-      const int d_lane = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-      unsigned a[8];
+    FaTrFrags kT;
+    tr_gather(k_lds, tro, kT);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int c = 0; c < 2; ++c)
+    for (int t = 0; t < 2; ++t) {
 #pragma unroll
-        for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            int kv = 16 * c + 8 * half + 4 * rr + kv_mate;
-            int dcol = (32 * t + d_lane) * 2;
-            a[c * 4 + rr * 2 + t] =
-                kbase + kv * 128 + (dcol ^ ((kv & 7) << 4));
-          }
-      uint2_t r[8];
-      asm volatile(
-          "ds_read_b64_tr_b16 %0, %8\n\t"
-          "ds_read_b64_tr_b16 %1, %9\n\t"
-          "ds_read_b64_tr_b16 %2, %10\n\t"
-          "ds_read_b64_tr_b16 %3, %11\n\t"
-          "ds_read_b64_tr_b16 %4, %12\n\t"
-          "ds_read_b64_tr_b16 %5, %13\n\t"
-          "ds_read_b64_tr_b16 %6, %14\n\t"
-          "ds_read_b64_tr_b16 %7, %15\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]),
-            "=&v"(r[4]), "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7])
-          : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]),
-            "v"(a[6]), "v"(a[7])
-          : "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
-          uint4_t w;
-          w[0] = r[c * 4 + 0 * 2 + t][0];
-          w[1] = r[c * 4 + 0 * 2 + t][1];
-          w[2] = r[c * 4 + 1 * 2 + t][0];
-          w[3] = r[c * 4 + 1 * 2 + t][1];
-          short8_t kf = __builtin_bit_cast(short8_t, w);
-          dqA[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gfA[c], kf,
-                                                           dqA[t], 0, 0, 0);
-          dqB[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gfB[c], kf,
-                                                           dqB[t], 0, 0, 0);
-        }
+      for (int c = 0; c < 2; ++c) {
+        short8_t kf = kT.frag(c, t);
+        dqA[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gfA[c], kf, dqA[t],
+                                                         0, 0, 0);
+        dqB[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gfB[c], kf, dqB[t],
+                                                         0, 0, 0);
       }
-      __builtin_amdgcn_s_setprio(0);
     }
+    __builtin_amdgcn_s_setprio(0);
   }
 
   // ---- epilogue ----
@@ -1078,13 +942,13 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   for (int t = 0; t < 2; ++t) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      int rloc = (r & 3) + 8 * (r >> 2) + 4 * half;
-      int qA = q_baseA + rloc, qB = q_baseB + rloc;
+      int rloc = c_row(r, half);
+      int qA = qb.qA + rloc, qB = qb.qB + rloc;
       if (qA < L)
-        dq[qkv_off + (long)qA * qkv_rs + 32 * t + col] =
+        dq[qkv_off + (long)qA * g.qkv_rs + 32 * t + col] =
             f32_to_bf16(dqA[t][r]);
       if (qB < L)
-        dq[qkv_off + (long)qB * qkv_rs + 32 * t + col] =
+        dq[qkv_off + (long)qB * g.qkv_rs + 32 * t + col] =
             f32_to_bf16(dqB[t][r]);
     }
   }
@@ -1094,53 +958,51 @@ extern "C" hipError_t flash_dq_recompute_launch(
     const void* q, const void* k, const void* v, const void* dout,
     const void* mask, const void* lse, const void* ddot, void* dq,
     int B, int H, int L, float scale, hipStream_t stream) {
-  int n_qblocks = (L + 2 * FA_QWG - 1) / (2 * FA_QWG);
-  dim3 grid(B * H * n_qblocks);
-  size_t shm = K_LDS_BYTES + VT_LDS_BYTES + 16;  // + tail-skip scratch
-  flash_dq_recompute_kernel<<<grid, FA_BLOCK, shm, stream>>>(
+  flash_dq_recompute_kernel<<<fa_grid(B, H, L, FA_Q2WG), FA_BLOCK,
+                              DQR_LDS_BYTES, stream>>>(
       (const short*)q, (const short*)k, (const short*)v, (const short*)dout,
       (const float*)mask, (const float*)lse, (const float*)ddot, (short*)dq,
-      B, H, L, scale,
-      (long)H * L * FA_DH, (long)L * FA_DH, FA_DH,
-      (long)H * L * FA_DH, (long)L * FA_DH, FA_DH);
+      B, H, L, scale, FaGeom::bhld(H, L));
   return hipGetLastError();
 }
 
+// packed: dq lands in the q third of dqkv [B, L, 3D]
 extern "C" hipError_t flash_dq_recompute_packed_launch(
     const void* qkv, const void* dout, const void* mask, const void* lse,
     const void* ddot, void* dqkv, int B, int H, int L, float scale,
     hipStream_t stream) {
   const int D = H * FA_DH;
-  int n_qblocks = (L + 2 * FA_QWG - 1) / (2 * FA_QWG);
-  dim3 grid(B * H * n_qblocks);
-  size_t shm = K_LDS_BYTES + VT_LDS_BYTES + 16;  // + tail-skip scratch
-  flash_dq_recompute_kernel<<<grid, FA_BLOCK, shm, stream>>>(
+  flash_dq_recompute_kernel<<<fa_grid(B, H, L, FA_Q2WG), FA_BLOCK,
+                              DQR_LDS_BYTES, stream>>>(
       (const short*)qkv, (const short*)qkv + D, (const short*)qkv + 2 * D,
       (const short*)dout, (const float*)mask, (const float*)lse,
       (const float*)ddot, (short*)dqkv,
-      B, H, L, scale,
-      (long)L * 3 * D, 64L, 3 * D,
-      (long)L * D, 64L, D);
+      B, H, L, scale, FaGeom::packed(H, L));
   return hipGetLastError();
 }
 
-// D = rowsum(dO * O) per (b, h, q) row — one wave per 4 rows (dh = 64).
-extern "C" __global__ void __launch_bounds__(256)
-fa_dot_kernel(const short* __restrict__ dout, const short* __restrict__ o,
-              float* __restrict__ ddot, long n_rows) {
-  // lane j of quarter-wave handles 4 bf16 (dh=64 -> 16 lanes x 4 elems)
-  long row = ((long)blockIdx.x * 256 + threadIdx.x) >> 4;
-  if (row >= n_rows) return;
-  int sub = threadIdx.x & 15;
-  const short* dr = dout + row * FA_DH + sub * 4;
-  const short* orow = o + row * FA_DH + sub * 4;
-  short4_t a = *(const short4_t*)dr;
-  short4_t c = *(const short4_t*)orow;
+// D = rowsum(dO * O) over one 64-element (b, h, q) row: 16 lanes x 4 bf16,
+// reduced across the 16-lane group.  Every lane of the group gets the sum.
+__device__ __forceinline__ float fa_row_dot(const short* dr, const short* orow,
+                                            int sub) {
+  short4_t a = *(const short4_t*)(dr + sub * 4);
+  short4_t c = *(const short4_t*)(orow + sub * 4);
   float s = 0.f;
 #pragma unroll
   for (int j = 0; j < 4; ++j) s += bf16_to_f32(a[j]) * bf16_to_f32(c[j]);
 #pragma unroll
   for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 16);
+  return s;
+}
+
+// dout/o [n_rows, 64] (any [B, H, L, 64]); ddot [n_rows].
+extern "C" __global__ void __launch_bounds__(256)
+fa_dot_kernel(const short* __restrict__ dout, const short* __restrict__ o,
+              float* __restrict__ ddot, long n_rows) {
+  long row = ((long)blockIdx.x * 256 + threadIdx.x) >> 4;
+  if (row >= n_rows) return;
+  int sub = threadIdx.x & 15;
+  float s = fa_row_dot(dout + row * FA_DH, o + row * FA_DH, sub);
   if (sub == 0) ddot[row] = s;
 }
 
@@ -1158,15 +1020,7 @@ fa_dot_packed_kernel(const short* __restrict__ dout,
   long bl = chunk / H;                     // b * L + l
   int l = (int)(bl % L);
   int b = (int)(bl / L);
-  const short* dr = dout + bl * D + h * FA_DH + sub * 4;
-  const short* orow = o + bl * D + h * FA_DH + sub * 4;
-  short4_t a = *(const short4_t*)dr;
-  short4_t c = *(const short4_t*)orow;
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) s += bf16_to_f32(a[j]) * bf16_to_f32(c[j]);
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 16);
+  float s = fa_row_dot(dout + bl * D + h * FA_DH, o + bl * D + h * FA_DH, sub);
   if (sub == 0) ddot[((long)b * H + h) * L + l] = s;
 }
 

@@ -102,6 +102,71 @@ void check_f32(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.device().is_cuda(), name, " must be on GPU");
 }
 
+// ---- flash-attention argument checks ----------------------------------------
+// The kernels index every operand from B, H, L alone, so each entry point
+// pins all shapes here, before any launch.
+
+struct FlashDims { long B, H, L; };
+using NamedTensor = std::pair<const char*, torch::Tensor>;
+
+// Optional additive key mask: f32, contiguous, on the GPU, exactly [B, L].
+const void* flash_mask_ptr(const c10::optional<torch::Tensor>& mask,
+                           const FlashDims& d) {
+  if (!mask.has_value()) return nullptr;
+  check_f32(*mask, "mask");
+  TORCH_CHECK(mask->dim() == 2 && mask->size(0) == d.B &&
+              mask->size(1) == d.L, "mask must be [B, L]");
+  return mask->data_ptr();
+}
+
+// Per-row f32 statistics (lse, ddot): [B, H, L].
+void check_flash_rows(std::initializer_list<NamedTensor> rows,
+                      const FlashDims& d) {
+  for (const auto& [name, t] : rows) {
+    check_f32(t, name);
+    TORCH_CHECK(t.dim() == 3 && t.size(0) == d.B && t.size(1) == d.H &&
+                t.size(2) == d.L, name, " must be [B, H, L]");
+  }
+}
+
+// [B, H, L, 64] family: `x` fixes the geometry, every tensor in `same` is
+// bf16 of the same shape, every tensor in `rows` is f32 [B, H, L].
+FlashDims check_flash_bhld(const char* xname, const torch::Tensor& x,
+                           std::initializer_list<NamedTensor> same,
+                           std::initializer_list<NamedTensor> rows) {
+  check_bf16(x, xname);
+  TORCH_CHECK(x.dim() == 4, xname, " must be [B, H, L, 64]");
+  const FlashDims d{x.size(0), x.size(1), x.size(2)};
+  TORCH_CHECK(x.size(3) == 64, "flash kernels are specialized for head_dim 64");
+  TORCH_CHECK(d.L % 32 == 0, "flash kernels need L % 32 == 0");
+  for (const auto& [name, t] : same) {
+    check_bf16(t, name);
+    TORCH_CHECK(t.sizes() == x.sizes(), name, " must match ", xname,
+                "'s shape");
+  }
+  check_flash_rows(rows, d);
+  return d;
+}
+
+// Packed family: qkv is [B, L, 3D] with D = H*64, every tensor in `outs` is
+// bf16 [B, L, D], every tensor in `rows` is f32 [B, H, L].
+FlashDims check_flash_packed(const torch::Tensor& qkv, long H,
+                             std::initializer_list<NamedTensor> outs,
+                             std::initializer_list<NamedTensor> rows) {
+  check_bf16(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 3, "qkv must be [B, L, 3D]");
+  const FlashDims d{qkv.size(0), H, qkv.size(1)};
+  TORCH_CHECK(qkv.size(2) == 3 * H * 64, "qkv last dim must be 3*H*64");
+  TORCH_CHECK(d.L % 32 == 0, "flash kernels need L % 32 == 0");
+  for (const auto& [name, t] : outs) {
+    check_bf16(t, name);
+    TORCH_CHECK(t.dim() == 3 && t.size(0) == d.B && t.size(1) == d.L &&
+                t.size(2) == H * 64, name, " must be [B, L, H*64]");
+  }
+  check_flash_rows(rows, d);
+  return d;
+}
+
 }  // namespace
 
 std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x,
@@ -333,18 +398,8 @@ std::vector<torch::Tensor> flash_fwd(torch::Tensor q, torch::Tensor k,
                                      torch::Tensor v,
                                      c10::optional<torch::Tensor> mask,
                                      double scale) {
-  check_bf16(q, "q"); check_bf16(k, "k"); check_bf16(v, "v");
-  TORCH_CHECK(q.dim() == 4, "q must be [B, H, L, dh]");
-  const long B = q.size(0), H = q.size(1), L = q.size(2), dh = q.size(3);
-  TORCH_CHECK(dh == 64, "flash_fwd is specialized for head_dim 64");
-  TORCH_CHECK(L % 32 == 0, "flash_fwd needs L % 32 == 0");
-  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes());
-  const void* mptr = nullptr;
-  if (mask.has_value()) {
-    check_f32(*mask, "mask");
-    TORCH_CHECK(mask->size(0) == B && mask->size(-1) == L, "mask is [B, L]");
-    mptr = mask->data_ptr();
-  }
+  const auto [B, H, L] = check_flash_bhld("q", q, {{"k", k}, {"v", v}}, {});
+  const void* mptr = flash_mask_ptr(mask, {B, H, L});
   auto o = torch::empty_like(q);
   auto lse = torch::empty({B, H, L}, q.options().dtype(torch::kFloat32));
   CHECK_HIP(flash_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), mptr,
@@ -376,6 +431,8 @@ torch::Tensor p_from_lse(torch::Tensor scores, c10::optional<torch::Tensor> mask
 
 torch::Tensor fa_dot(torch::Tensor dout, torch::Tensor o) {
   check_bf16(dout, "dout"); check_bf16(o, "o");
+  TORCH_CHECK(dout.dim() == 4 && o.sizes() == dout.sizes(),
+              "dout and o must both be [B, H, L, 64]");
   const long n_rows = dout.numel() / dout.size(-1);
   TORCH_CHECK(dout.size(-1) == 64, "fa_dot expects head_dim 64");
   auto d = torch::empty({n_rows}, dout.options().dtype(torch::kFloat32));
@@ -390,17 +447,12 @@ std::vector<torch::Tensor> flash_bwd_fused(torch::Tensor q, torch::Tensor k,
                                            torch::Tensor lse,
                                            torch::Tensor ddot, double scale,
                                            bool emit_ds) {
-  check_bf16(q, "q"); check_bf16(k, "k"); check_bf16(v, "v");
-  check_bf16(dout, "dout"); check_f32(lse, "lse"); check_f32(ddot, "ddot");
-  const long B = q.size(0), H = q.size(1), L = q.size(2);
-  TORCH_CHECK(q.size(3) == 64 && L % 32 == 0, "dh=64 and L%32==0 required");
-  const void* mptr = nullptr;
-  if (mask.has_value()) {
-    check_f32(*mask, "mask");
-    mptr = mask->data_ptr();
-  }
-  // emit_ds=false (the default path since round 2): no [B, H, L, L] dS
-  // materialization — dQ comes from flash_dq_recompute instead.
+  const auto [B, H, L] = check_flash_bhld(
+      "q", q, {{"k", k}, {"v", v}, {"dout", dout}},
+      {{"lse", lse}, {"ddot", ddot}});
+  const void* mptr = flash_mask_ptr(mask, {B, H, L});
+  // emit_ds=false (the default): no [B, H, L, L] dS materialization — dQ
+  // comes from flash_dq_recompute instead.
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
   torch::Tensor ds;
@@ -460,17 +512,10 @@ std::vector<torch::Tensor> flash_fwd_packed(torch::Tensor qkv, long H,
                                             c10::optional<torch::Tensor> mask,
                                             double scale) {
   // qkv: [B, L, 3D] packed projection output, D = H*64
-  check_bf16(qkv, "qkv");
-  TORCH_CHECK(qkv.dim() == 3, "qkv must be [B, L, 3D]");
-  const long B = qkv.size(0), L = qkv.size(1), D3 = qkv.size(2);
-  TORCH_CHECK(D3 == 3 * H * 64, "qkv last dim must be 3*H*64");
-  TORCH_CHECK(L % 32 == 0, "L % 32 == 0 required");
-  const void* mptr = nullptr;
-  if (mask.has_value()) {
-    check_f32(*mask, "mask");
-    mptr = mask->data_ptr();
-  }
-  auto o = torch::empty({B, L, D3 / 3}, qkv.options());
+  const auto dims = check_flash_packed(qkv, H, {}, {});
+  const long B = dims.B, L = dims.L;
+  const void* mptr = flash_mask_ptr(mask, dims);
+  auto o = torch::empty({B, L, H * 64}, qkv.options());
   auto lse = torch::empty({B, H, L}, qkv.options().dtype(torch::kFloat32));
   CHECK_HIP(flash_fwd_packed_launch(qkv.data_ptr(), mptr, o.data_ptr(),
                                     lse.data_ptr(), (int)B, (int)H, (int)L,
@@ -483,15 +528,10 @@ torch::Tensor flash_bwd_packed(torch::Tensor qkv, torch::Tensor o,
                                c10::optional<torch::Tensor> mask,
                                torch::Tensor lse, long H, double scale) {
   // full packed backward: ddot + dK/dV + dQ, all into one [B, L, 3D] grad
-  check_bf16(qkv, "qkv"); check_bf16(o, "o"); check_bf16(dout, "dout");
-  check_f32(lse, "lse");
-  const long B = qkv.size(0), L = qkv.size(1), D3 = qkv.size(2);
-  TORCH_CHECK(D3 == 3 * H * 64 && L % 32 == 0, "bad packed shapes");
-  const void* mptr = nullptr;
-  if (mask.has_value()) {
-    check_f32(*mask, "mask");
-    mptr = mask->data_ptr();
-  }
+  const auto dims = check_flash_packed(qkv, H, {{"o", o}, {"dout", dout}},
+                                       {{"lse", lse}});
+  const long B = dims.B, L = dims.L;
+  const void* mptr = flash_mask_ptr(mask, dims);
   auto ddot = torch::empty({B, H, L}, qkv.options().dtype(torch::kFloat32));
   CHECK_HIP(fa_dot_packed_launch(dout.data_ptr(), o.data_ptr(),
                                  ddot.data_ptr(), (int)B, (int)H, (int)L,
@@ -511,15 +551,10 @@ torch::Tensor flash_dq_recompute(torch::Tensor q, torch::Tensor k,
                                  c10::optional<torch::Tensor> mask,
                                  torch::Tensor lse, torch::Tensor ddot,
                                  double scale) {
-  check_bf16(q, "q"); check_bf16(k, "k"); check_bf16(v, "v");
-  check_bf16(dout, "dout"); check_f32(lse, "lse"); check_f32(ddot, "ddot");
-  const long B = q.size(0), H = q.size(1), L = q.size(2);
-  TORCH_CHECK(q.size(3) == 64 && L % 32 == 0, "dh=64 and L%32==0 required");
-  const void* mptr = nullptr;
-  if (mask.has_value()) {
-    check_f32(*mask, "mask");
-    mptr = mask->data_ptr();
-  }
+  const auto [B, H, L] = check_flash_bhld(
+      "q", q, {{"k", k}, {"v", v}, {"dout", dout}},
+      {{"lse", lse}, {"ddot", ddot}});
+  const void* mptr = flash_mask_ptr(mask, {B, H, L});
   auto dq = torch::empty_like(q);
   CHECK_HIP(flash_dq_recompute_launch(q.data_ptr(), k.data_ptr(),
                                       v.data_ptr(), dout.data_ptr(), mptr,
@@ -530,10 +565,10 @@ torch::Tensor flash_dq_recompute(torch::Tensor q, torch::Tensor k,
 }
 
 torch::Tensor flash_dq(torch::Tensor ds, torch::Tensor k) {
-  check_bf16(ds, "ds"); check_bf16(k, "k");
-  const long B = k.size(0), H = k.size(1), L = k.size(2);
-  TORCH_CHECK(k.size(3) == 64 && L % 32 == 0, "dh=64 and L%32==0 required");
-  TORCH_CHECK(ds.size(2) == L && ds.size(3) == L, "ds must be [B,H,L,L]");
+  const auto [B, H, L] = check_flash_bhld("k", k, {}, {});
+  check_bf16(ds, "ds");
+  TORCH_CHECK(ds.dim() == 4 && ds.size(0) == B && ds.size(1) == H &&
+              ds.size(2) == L && ds.size(3) == L, "ds must be [B, H, L, L]");
   auto dq = torch::empty_like(k);
   CHECK_HIP(flash_dq_launch(ds.data_ptr(), k.data_ptr(), dq.data_ptr(),
                             (int)B, (int)H, (int)L, cur_stream()));

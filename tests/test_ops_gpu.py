@@ -257,16 +257,22 @@ def test_p_from_lse_rows_normalized():
     assert torch.allclose(sums, torch.ones_like(sums), atol=3e-2)
 
 
-def test_flash_bwd_fused_vs_reference():
+@pytest.mark.parametrize("L,pad_from", [(128, 100), (256, 96)])
+def test_flash_bwd_fused_vs_reference(L, pad_from):
+    """Batch row 0 is padded from `pad_from`, row 1 is unpadded.  At
+    (256, 96) the padded row drives every padding shortcut: backward
+    workgroup 1 (kv 128..255) takes the whole-workgroup early-out, wave 3 of
+    workgroup 0 (kv 96..127) the per-wave skip, and the forward and
+    dq-recompute tail skip stops after 3 of 8 kv tiles."""
     torch.manual_seed(14)
-    B, H, L = 2, 2, 128
+    B, H = 2, 2
     scale = 0.125
     q = _bf16(torch.randn(B, H, L, 64))
     k = _bf16(torch.randn(B, H, L, 64))
     v = _bf16(torch.randn(B, H, L, 64))
     do = _bf16(torch.randn(B, H, L, 64))
     mask = torch.zeros(B, L)
-    mask[:, 100:] = -1e9
+    mask[0, pad_from:] = -1e9
     mg = mask.cuda().contiguous()
     o, lse = ops.hip_ops().flash_fwd(q, k, v, mg, scale)
     ddot = ops.hip_ops().fa_dot(do, o)
@@ -288,15 +294,50 @@ def test_flash_bwd_fused_vs_reference():
         (dvg.float() - dv_ref).abs().max()
     assert torch.allclose(dkg.float(), dk_ref, atol=5e-2, rtol=3e-2), \
         (dkg.float() - dk_ref).abs().max()
-    # default path returns dk/dv only (no dS materialization)
+    # default path returns dk/dv only (no dS materialization); emit_ds=True
+    # above disables the padding early-out, so this also compares the
+    # skipped path bit for bit with the unskipped one
     dk2, dv2 = ops.hip_ops().flash_bwd_fused(q, k, v, do, mg, lse,
                                              ddot, scale)
     assert torch.equal(dk2, dkg) and torch.equal(dv2, dvg)
-    # round-2 dQ-by-recompute kernel vs the fp32 reference
+    # dQ-by-recompute kernel vs the fp32 reference
     dqg = ops.hip_ops().flash_dq_recompute(q, k, v, do, mg, lse, ddot, scale)
     dq_ref = torch.matmul(ds_ref, k.float())
     assert torch.allclose(dqg.float(), dq_ref, atol=5e-2, rtol=3e-2), \
         (dqg.float() - dq_ref).abs().max()
+
+
+def test_flash_rejects_wrong_mask_and_lse_shapes():
+    """A short mask or lse must be refused by the binding (TORCH_CHECK), not
+    reach a kernel that would read past its end."""
+    torch.manual_seed(29)
+    ext = ops.hip_ops()
+    B, H, L = 1, 1, 64
+    scale = 0.125
+    q, k, v, do = (_bf16(torch.randn(B, H, L, 64)) for _ in range(4))
+    o, lse = ext.flash_fwd(q, k, v, None, scale)
+    ddot = ext.fa_dot(do, o)
+    qkv = torch.cat([t.transpose(1, 2).reshape(B, L, H * 64)
+                     for t in (q, k, v)], dim=-1).contiguous()
+    o_p = o.transpose(1, 2).reshape(B, L, H * 64).contiguous()
+    do_p = do.transpose(1, 2).reshape(B, L, H * 64).contiguous()
+    bad_mask = torch.zeros(B, L // 2, device="cuda")
+    bad_lse = lse[:, :, :L // 2].contiguous()
+
+    with pytest.raises(RuntimeError):
+        ext.flash_fwd(q, k, v, bad_mask, scale)
+    with pytest.raises(RuntimeError):
+        ext.flash_bwd_fused(q, k, v, do, bad_mask, lse, ddot, scale)
+    with pytest.raises(RuntimeError):
+        ext.flash_bwd_fused(q, k, v, do, None, bad_lse, ddot, scale)
+    with pytest.raises(RuntimeError):
+        ext.flash_dq_recompute(q, k, v, do, bad_mask, lse, ddot, scale)
+    with pytest.raises(RuntimeError):
+        ext.flash_dq_recompute(q, k, v, do, None, bad_lse, ddot, scale)
+    with pytest.raises(RuntimeError):
+        ext.flash_bwd_packed(qkv, o_p, do_p, bad_mask, lse, H, scale)
+    with pytest.raises(RuntimeError):
+        ext.flash_bwd_packed(qkv, o_p, do_p, None, bad_lse, H, scale)
 
 
 def test_layernorm_bwd_with_residual_grad():
