@@ -41,13 +41,16 @@ typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
 // LDS (dynamic, 16-B aligned).  One staged tile is [32][64] bf16, row
 // stride 128 B, XOR-swizzled = 4096 B.  Per kernel:
 //  fwd:          K tile | V tile | alpha [4 waves][64] f32 (1024 B; its
-//                first word doubles as the tail-skip scratch before the loop)
+//                first words double as the tail-skip / segment-range scratch
+//                before the loop)
 //  bwd_fused:    Q tile | dO tile | lse [32] f32 | ddot [32] f32
+//                (segmented: + the staged tile's q segment ids [32] i32)
 //  dq:           K tile
 //  dq_recompute: K tile | V tile | 16 B tail-skip scratch
 #define TILE_LDS_BYTES (FA_KVB * 128)
 #define FWD_LDS_BYTES (2 * TILE_LDS_BYTES + FA_WAVES * 64 * sizeof(float))
 #define BWD_LDS_BYTES (2 * TILE_LDS_BYTES + 64 * sizeof(float))
+#define BWD_SEG_LDS_BYTES (BWD_LDS_BYTES + 32 * sizeof(int))
 #define DQ_LDS_BYTES TILE_LDS_BYTES
 #define DQR_LDS_BYTES (2 * TILE_LDS_BYTES + 16)
 
@@ -256,9 +259,61 @@ __device__ __forceinline__ int fa_last_active_kv(const float* mrow, int L,
   return *scratch;
 }
 
-extern "C" __global__ void __launch_bounds__(FA_BLOCK, 2)
+// ---- segments (sequence packing) --------------------------------------------
+// seg is int32 [B, L], non-decreasing along a row; position i attends to
+// position j iff seg[b, i] == seg[b, j].  The padding tail of a row carries
+// one id above every real id, so pads form their own trailing segment and
+// no softmax row is empty.  The bias is the padding mask's: 0 inside the
+// segment, -1e9 outside, so an out-of-segment probability is exactly +0.0f
+// in forward (a running max left behind by an all-foreign tile is
+// annihilated by alpha == 0 at the first own tile) and in both backward
+// kernels.  That exact zero is what lets whole tiles be skipped.
+#define FA_SEG_BIAS -1.0e9f
+
+// Tile-range skip: ids are monotone, so the positions that matter to rows
+// [r_lo, r_hi] of a workgroup form ONE contiguous range — from the first
+// position of r_lo's segment to the last position of r_hi's.  Computed once
+// per workgroup by a scan of the seg row (like fa_last_active_kv).  The
+// result always contains [r_lo, r_hi] and lies inside [0, L): a seg row
+// that breaks the monotone contract changes numbers, never addresses.
+struct FaRange { int lo, hi; };
+
+__device__ __forceinline__ FaRange fa_seg_range(const int* srow, int L,
+                                                int r_lo, int r_hi, int tid,
+                                                int* scratch) {
+  const int s_first = srow[r_lo], s_last = srow[r_hi];
+  if (tid == 0) { scratch[0] = r_lo; scratch[1] = r_hi; }
+  __syncthreads();
+  int lo = r_lo, hi = r_hi;
+  for (int j = tid; j < L; j += FA_BLOCK) {
+    const int s = srow[j];
+    if (s == s_first) lo = min(lo, j);
+    if (s == s_last) hi = max(hi, j);
+  }
+  atomicMin(&scratch[0], lo);
+  atomicMax(&scratch[1], hi);
+  __syncthreads();
+  return {scratch[0], scratch[1]};
+}
+
+// Inside the range a wave still meets tiles that hold none of its own rows'
+// segments (a 256-token row of ~36-token examples is mostly such tiles).
+// Every probability of such a tile is +0.0f for this wave, so its MFMA and
+// softmax work is skipped; the staging and the barriers are not.  r is one
+// id per register row, a and b the lane's two ids (pass a twice for one).
+__device__ __forceinline__ bool fa_seg_tile_live(const int (&r)[16], int a,
+                                                 int b) {
+  bool hit = false;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) hit |= (r[i] == a) | (r[i] == b);
+  return __builtin_amdgcn_ballot_w64(hit) != 0;
+}
+
+template <bool SEG>
+__global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
                  const short* __restrict__ v, const float* __restrict__ mask,
+                 const int* __restrict__ seg,
                  short* __restrict__ o, float* __restrict__ lse,
                  int B, int H, int L, float scale, FaGeom g) {
   // Each wave processes TWO independent 32-row q-blocks against the shared
@@ -285,7 +340,14 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
   const int my_qB = qb.qB + col;
   const bool validA = my_qA < L;
   const bool validB = my_qB < L;
-  const float* mrow = mask ? mask + (long)b * L : nullptr;
+  const float* mrow = (!SEG && mask) ? mask + (long)b * L : nullptr;
+  const int* srow = SEG ? seg + (long)b * L : nullptr;
+  // q segment ids: one lane-local scalar per q-block
+  int sqA = 0, sqB = 0;
+  if constexpr (SEG) {
+    sqA = srow[validA ? my_qA : L - 1];
+    sqB = srow[validB ? my_qB : L - 1];
+  }
 
   short8_t qfA[4], qfB[4];
   {
@@ -304,15 +366,23 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
   float mA = -3.0e38f, lA = 0.f, mB = -3.0e38f, lB = 0.f;
 
   const int n_kv = L / FA_KVB;
+  int kt_begin = 0;
   int n_kv_eff = n_kv;
   if (mrow) {
     int last = fa_last_active_kv(mrow, L, tid, (int*)alpha_lds);
     if (last >= 0) n_kv_eff = min(n_kv, last / FA_KVB + 1);
   }
+  if constexpr (SEG) {
+    const int q_lo = qb.qA - wid * FA_QB;        // the workgroup's first q row
+    const FaRange kr = fa_seg_range(srow, L, q_lo, min(q_lo + FA_Q2WG, L) - 1,
+                                    tid, (int*)alpha_lds);
+    kt_begin = kr.lo / FA_KVB;
+    n_kv_eff = kr.hi / FA_KVB + 1;
+  }
   const FaStager st(tid);
-  short8_t kv8 = st.load(k + qkv_off, 0, g.qkv_rs);
-  short8_t vv8 = st.load(v + qkv_off, 0, g.qkv_rs);
-  for (int kt = 0; kt < n_kv_eff; ++kt) {
+  short8_t kv8 = st.load(k + qkv_off, kt_begin * FA_KVB, g.qkv_rs);
+  short8_t vv8 = st.load(v + qkv_off, kt_begin * FA_KVB, g.qkv_rs);
+  for (int kt = kt_begin; kt < n_kv_eff; ++kt) {
     const int kv0 = kt * FA_KVB;
     __syncthreads();
     st.store(k_lds, kv8);
@@ -325,11 +395,18 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
 
     // mask-bias loads HOISTED above the QK chain: issued per register
     // inside the softmax loop they sit exposed on the serial path between
-    // the mfma results and the exp chain
+    // the mfma results and the exp chain.  The kv segment ids take the
+    // bias's place, per register, hoisted the same way.
     float mb_r[16];
+    int sk_r[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r)
-      mb_r[r] = mrow ? mrow[kv0 + c_row(r, half)] : 0.f;
+    for (int r = 0; r < 16; ++r) {
+      if constexpr (SEG) sk_r[r] = srow[kv0 + c_row(r, half)];
+      else mb_r[r] = mrow ? mrow[kv0 + c_row(r, half)] : 0.f;
+    }
+    if constexpr (SEG) {
+      if (!fa_seg_tile_live(sk_r, sqA, sqB)) continue;
+    }
 
     // ---- QK^T for BOTH q-blocks (8 back-to-back MFMAs) ----
     f32x16 sA = (f32x16)(0.f), sB = (f32x16)(0.f);
@@ -347,9 +424,15 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
     float tmaxA = -3.0e38f, tmaxB = -3.0e38f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      float mb = mb_r[r];
-      float xA = sA[r] * scale + mb;
-      float xB = sB[r] * scale + mb;
+      float mbA, mbB;
+      if constexpr (SEG) {
+        mbA = sk_r[r] == sqA ? 0.f : FA_SEG_BIAS;
+        mbB = sk_r[r] == sqB ? 0.f : FA_SEG_BIAS;
+      } else {
+        mbA = mbB = mb_r[r];
+      }
+      float xA = sA[r] * scale + mbA;
+      float xB = sB[r] * scale + mbB;
       svA[r] = xA; svB[r] = xB;
       tmaxA = fmaxf(tmaxA, xA);
       tmaxB = fmaxf(tmaxB, xB);
@@ -446,30 +529,45 @@ static dim3 fa_grid(int B, int H, int L, int rows_per_wg) {
   return dim3(B * H * ((L + rows_per_wg - 1) / rows_per_wg));
 }
 
+// Every launcher below takes an optional seg (int32 [B, L], nullptr = none)
+// and picks the segmented instantiation when it is given; mask and seg are
+// mutually exclusive (the bindings enforce it).
+static void fa_fwd_dispatch(const short* q, const short* k, const short* v,
+                            const void* mask, const void* seg, void* o,
+                            void* lse, int B, int H, int L, float scale,
+                            FaGeom g, hipStream_t stream) {
+  const dim3 grid = fa_grid(B, H, L, FA_Q2WG);
+  if (seg)
+    flash_fwd_kernel<true><<<grid, FA_BLOCK, FWD_LDS_BYTES, stream>>>(
+        q, k, v, nullptr, (const int*)seg, (short*)o, (float*)lse, B, H, L,
+        scale, g);
+  else
+    flash_fwd_kernel<false><<<grid, FA_BLOCK, FWD_LDS_BYTES, stream>>>(
+        q, k, v, (const float*)mask, nullptr, (short*)o, (float*)lse, B, H, L,
+        scale, g);
+}
+
 extern "C" hipError_t flash_fwd_launch(const void* q, const void* k,
                                        const void* v, const void* mask,
-                                       void* o, void* lse, int B, int H,
-                                       int L, float scale,
+                                       const void* seg, void* o, void* lse,
+                                       int B, int H, int L, float scale,
                                        hipStream_t stream) {
-  flash_fwd_kernel<<<fa_grid(B, H, L, FA_Q2WG), FA_BLOCK, FWD_LDS_BYTES,
-                     stream>>>(
-      (const short*)q, (const short*)k, (const short*)v, (const float*)mask,
-      (short*)o, (float*)lse, B, H, L, scale, FaGeom::bhld(H, L));
+  fa_fwd_dispatch((const short*)q, (const short*)k, (const short*)v, mask,
+                  seg, o, lse, B, H, L, scale, FaGeom::bhld(H, L), stream);
   return hipGetLastError();
 }
 
 // qkv: [B, L, 3D] packed projection output (D = H*64); o: [B, L, D]
 extern "C" hipError_t flash_fwd_packed_launch(const void* qkv,
-                                              const void* mask, void* o,
+                                              const void* mask,
+                                              const void* seg, void* o,
                                               void* lse, int B, int H, int L,
                                               float scale,
                                               hipStream_t stream) {
   const int D = H * FA_DH;
-  flash_fwd_kernel<<<fa_grid(B, H, L, FA_Q2WG), FA_BLOCK, FWD_LDS_BYTES,
-                     stream>>>(
-      (const short*)qkv, (const short*)qkv + D, (const short*)qkv + 2 * D,
-      (const float*)mask, (short*)o, (float*)lse, B, H, L, scale,
-      FaGeom::packed(H, L));
+  fa_fwd_dispatch((const short*)qkv, (const short*)qkv + D,
+                  (const short*)qkv + 2 * D, mask, seg, o, lse, B, H, L,
+                  scale, FaGeom::packed(H, L), stream);
   return hipGetLastError();
 }
 
@@ -502,11 +600,19 @@ extern "C" hipError_t flash_fwd_packed_launch(const void* qkv,
 // Mirrors reference capability only in spirit: the reference ships no
 // attention kernels (data-only replication package).
 
-extern "C" __global__ void __launch_bounds__(FA_BLOCK, 2)
+//
+// Segmented (SEG): the kv segment id is one scalar per lane, the q ids of
+// the staged tile go through LDS next to lse/ddot, and only the q tiles
+// inside the mirrored fa_seg_range of the workgroup's 128 kv rows are
+// visited.  SEG excludes mask and the dS output.
+
+template <bool SEG>
+__global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
                        const short* __restrict__ v,
                        const short* __restrict__ dout,
                        const float* __restrict__ mask,
+                       const int* __restrict__ seg,
                        const float* __restrict__ lse,
                        const float* __restrict__ ddot,
                        short* __restrict__ ds, short* __restrict__ dk,
@@ -517,6 +623,7 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   short* do_lds = (short*)(smem + TILE_LDS_BYTES);
   float* lse_lds = (float*)(smem + 2 * TILE_LDS_BYTES);  // [32]
   float* dd_lds = lse_lds + 32;                          // [32]
+  int* seg_lds = (int*)(dd_lds + 32);                    // [32], SEG only
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
@@ -537,8 +644,11 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   const int kv_base = kb * FA_QWG + wid * FA_KVB;     // this wave's 32 kv rows
   const int my_kv = kv_base + col;
   const bool kv_valid = my_kv < L;                    // L%32==0: whole block
-  const float* mrow = mask ? mask + (long)b * L : nullptr;
+  const float* mrow = (!SEG && mask) ? mask + (long)b * L : nullptr;
   const float mb = mrow ? mrow[min(my_kv, L - 1)] : 0.f;
+  const int* srow = SEG ? seg + (long)b * L : nullptr;
+  int sk = 0;                                         // kv segment id (lane)
+  if constexpr (SEG) sk = srow[min(my_kv, L - 1)];
 
   // Early-out: if every kv row this workgroup owns is padding
   // (bias <= -1e8) and the sequence has at least one real token, P and dS
@@ -586,11 +696,19 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
     dk_acc[t] = (f32x16)(0.f);
   }
   if (!skip_tile) {
-  const int n_q = L / 32;
+  int qt_begin = 0;
+  int n_q = L / 32;
+  if constexpr (SEG) {
+    const int kv_lo = kb * FA_QWG;                    // the workgroup's kv rows
+    const FaRange qr = fa_seg_range(srow, L, kv_lo, min(kv_lo + FA_QWG, L) - 1,
+                                    tid, (int*)lse_lds);
+    qt_begin = qr.lo / 32;
+    n_q = qr.hi / 32 + 1;
+  }
   const FaStager st(tid);
-  short8_t qv8 = st.load(q + qkv_off, 0, g.qkv_rs);
-  short8_t dv8 = st.load(dout + o_off, 0, g.o_rs);
-  for (int qt = 0; qt < n_q; ++qt) {
+  short8_t qv8 = st.load(q + qkv_off, qt_begin * 32, g.qkv_rs);
+  short8_t dv8 = st.load(dout + o_off, qt_begin * 32, g.o_rs);
+  for (int qt = qt_begin; qt < n_q; ++qt) {
     const int q0 = qt * 32;
     __syncthreads();
     st.store(q_lds, qv8);
@@ -598,6 +716,7 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
     if (tid < 32) {
       lse_lds[tid] = lse[(long)bh * L + q0 + tid];
       dd_lds[tid] = ddot[(long)bh * L + q0 + tid];
+      if constexpr (SEG) seg_lds[tid] = srow[q0 + tid];
     }
     __syncthreads();
     if (qt + 1 < n_q) {
@@ -606,6 +725,14 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
     }
 
     if (wave_skip) continue;
+    // q segment ids of the staged tile, by register row; a tile that holds
+    // none of this wave's kv segments contributes exact zeros
+    int sq_r[16];
+    if constexpr (SEG) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sq_r[r] = seg_lds[c_row(r, half)];
+      if (!fa_seg_tile_live(sq_r, sk, sk)) continue;
+    }
     // S[q, kv] and dP[q, kv]: reg=q rows, lane=kv cols
     f32x16 s_acc = (f32x16)(0.f);
     f32x16 dp_acc = (f32x16)(0.f);
@@ -626,12 +753,14 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int ql = c_row(r, half);
-      pv[r] = __expf(s_acc[r] * scale + mb - lse_lds[ql]);
+      float bias = mb;
+      if constexpr (SEG) bias = sq_r[r] == sk ? 0.f : FA_SEG_BIAS;
+      pv[r] = __expf(s_acc[r] * scale + bias - lse_lds[ql]);
       gv[r] = scale * pv[r] * (dp_acc[r] - dd_lds[ql]);
     }
     // dS out, natural [q, kv] rows (2 B per lane, lanes contiguous in kv);
     // only on the A/B path that feeds flash_dq_kernel
-    if (ds != nullptr && kv_valid) {
+    if (!SEG && ds != nullptr && kv_valid) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         ds[bh_sq + (long)(q0 + c_row(r, half)) * L + my_kv] =
@@ -676,31 +805,50 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   }
 }
 
+static void fa_bwd_fused_dispatch(const short* q, const short* k,
+                                  const short* v, const void* dout,
+                                  const void* mask, const void* seg,
+                                  const void* lse, const void* ddot, void* ds,
+                                  short* dk, short* dv, int B, int H, int L,
+                                  float scale, FaGeom g, hipStream_t stream) {
+  const dim3 grid = fa_grid(B, H, L, FA_QWG);
+  if (seg)
+    flash_bwd_fused_kernel<true><<<grid, FA_BLOCK, BWD_SEG_LDS_BYTES,
+                                   stream>>>(
+        q, k, v, (const short*)dout, nullptr, (const int*)seg,
+        (const float*)lse, (const float*)ddot, nullptr, dk, dv, B, H, L,
+        scale, g);
+  else
+    flash_bwd_fused_kernel<false><<<grid, FA_BLOCK, BWD_LDS_BYTES, stream>>>(
+        q, k, v, (const short*)dout, (const float*)mask, nullptr,
+        (const float*)lse, (const float*)ddot, (short*)ds, dk, dv, B, H, L,
+        scale, g);
+}
+
+// seg excludes the dS output: with seg given, ds must be nullptr
 extern "C" hipError_t flash_bwd_fused_launch(
     const void* q, const void* k, const void* v, const void* dout,
-    const void* mask, const void* lse, const void* ddot, void* ds, void* dk,
-    void* dv, int B, int H, int L, float scale, hipStream_t stream) {
-  flash_bwd_fused_kernel<<<fa_grid(B, H, L, FA_QWG), FA_BLOCK, BWD_LDS_BYTES,
-                           stream>>>(
-      (const short*)q, (const short*)k, (const short*)v, (const short*)dout,
-      (const float*)mask, (const float*)lse, (const float*)ddot, (short*)ds,
-      (short*)dk, (short*)dv, B, H, L, scale, FaGeom::bhld(H, L));
+    const void* mask, const void* seg, const void* lse, const void* ddot,
+    void* ds, void* dk, void* dv, int B, int H, int L, float scale,
+    hipStream_t stream) {
+  if (seg && ds) return hipErrorInvalidValue;
+  fa_bwd_fused_dispatch((const short*)q, (const short*)k, (const short*)v,
+                        dout, mask, seg, lse, ddot, ds, (short*)dk,
+                        (short*)dv, B, H, L, scale, FaGeom::bhld(H, L),
+                        stream);
   return hipGetLastError();
 }
 
 // packed: qkv/dqkv [B, L, 3D], dout [B, L, D]; dk/dv land inside dqkv
 extern "C" hipError_t flash_bwd_fused_packed_launch(
-    const void* qkv, const void* dout, const void* mask, const void* lse,
-    const void* ddot, void* dqkv, int B, int H, int L, float scale,
-    hipStream_t stream) {
+    const void* qkv, const void* dout, const void* mask, const void* seg,
+    const void* lse, const void* ddot, void* dqkv, int B, int H, int L,
+    float scale, hipStream_t stream) {
   const int D = H * FA_DH;
-  flash_bwd_fused_kernel<<<fa_grid(B, H, L, FA_QWG), FA_BLOCK, BWD_LDS_BYTES,
-                           stream>>>(
-      (const short*)qkv, (const short*)qkv + D, (const short*)qkv + 2 * D,
-      (const short*)dout, (const float*)mask, (const float*)lse,
-      (const float*)ddot, nullptr,
-      (short*)dqkv + D, (short*)dqkv + 2 * D, B, H, L, scale,
-      FaGeom::packed(H, L));
+  fa_bwd_fused_dispatch((const short*)qkv, (const short*)qkv + D,
+                        (const short*)qkv + 2 * D, dout, mask, seg, lse, ddot,
+                        nullptr, (short*)dqkv + D, (short*)dqkv + 2 * D, B, H,
+                        L, scale, FaGeom::packed(H, L), stream);
   return hipGetLastError();
 }
 
@@ -809,12 +957,16 @@ extern "C" hipError_t flash_dq_launch(const void* ds, const void* k, void* dq,
 //   dS = scale * P * (dP - D) in registers
 //   dS -> A-fragments [row=q][k=kv]
 //   dQ[q, d] += mfma(dS-frag, K^T-frag), K^T gathered from the staged K tile
-extern "C" __global__ void __launch_bounds__(FA_BLOCK, 2)
+// Segmented (SEG): as in flash_fwd — q ids lane-local, kv ids per register,
+// kv tiles limited to the workgroup's fa_seg_range.
+template <bool SEG>
+__global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_dq_recompute_kernel(const short* __restrict__ q,
                           const short* __restrict__ k,
                           const short* __restrict__ v,
                           const short* __restrict__ dout,
                           const float* __restrict__ mask,
+                          const int* __restrict__ seg,
                           const float* __restrict__ lse,
                           const float* __restrict__ ddot,
                           short* __restrict__ dq,
@@ -840,7 +992,13 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   const int my_qB = qb.qB + col;
   const bool validA = my_qA < L;
   const bool validB = my_qB < L;
-  const float* mrow = mask ? mask + (long)b * L : nullptr;
+  const float* mrow = (!SEG && mask) ? mask + (long)b * L : nullptr;
+  const int* srow = SEG ? seg + (long)b * L : nullptr;
+  int sqA = 0, sqB = 0;
+  if constexpr (SEG) {
+    sqA = srow[validA ? my_qA : L - 1];
+    sqB = srow[validB ? my_qB : L - 1];
+  }
 
   short8_t qfA[4], qfB[4], dofA[4], dofB[4];
   {
@@ -866,15 +1024,23 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   for (int t = 0; t < 2; ++t) { dqA[t] = (f32x16)(0.f); dqB[t] = (f32x16)(0.f); }
 
   const int n_kv = L / FA_KVB;
+  int kt_begin = 0;
   int n_kv_eff = n_kv;
   if (mrow) {
     int last = fa_last_active_kv(mrow, L, tid, skip_scratch);
     if (last >= 0) n_kv_eff = min(n_kv, last / FA_KVB + 1);
   }
+  if constexpr (SEG) {
+    const int q_lo = qb.qA - wid * FA_QB;        // the workgroup's first q row
+    const FaRange kr = fa_seg_range(srow, L, q_lo, min(q_lo + FA_Q2WG, L) - 1,
+                                    tid, skip_scratch);
+    kt_begin = kr.lo / FA_KVB;
+    n_kv_eff = kr.hi / FA_KVB + 1;
+  }
   const FaStager st(tid);
-  short8_t kv8 = st.load(k + qkv_off, 0, g.qkv_rs);
-  short8_t vv8 = st.load(v + qkv_off, 0, g.qkv_rs);
-  for (int kt = 0; kt < n_kv_eff; ++kt) {
+  short8_t kv8 = st.load(k + qkv_off, kt_begin * FA_KVB, g.qkv_rs);
+  short8_t vv8 = st.load(v + qkv_off, kt_begin * FA_KVB, g.qkv_rs);
+  for (int kt = kt_begin; kt < n_kv_eff; ++kt) {
     const int kv0 = kt * FA_KVB;
     __syncthreads();
     st.store(k_lds, kv8);
@@ -886,9 +1052,15 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
     }
 
     float mb_r[16];
+    int sk_r[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r)
-      mb_r[r] = mrow ? mrow[kv0 + c_row(r, half)] : 0.f;
+    for (int r = 0; r < 16; ++r) {
+      if constexpr (SEG) sk_r[r] = srow[kv0 + c_row(r, half)];
+      else mb_r[r] = mrow ? mrow[kv0 + c_row(r, half)] : 0.f;
+    }
+    if constexpr (SEG) {
+      if (!fa_seg_tile_live(sk_r, sqA, sqB)) continue;
+    }
 
     // ---- S and dP for BOTH q-blocks (16 back-to-back MFMAs) ----
     f32x16 sA = (f32x16)(0.f), sB = (f32x16)(0.f);
@@ -909,8 +1081,15 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
     float gA[16], gB[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      float expA = __expf(sA[r] * scale + mb_r[r] - lseA);
-      float expB = __expf(sB[r] * scale + mb_r[r] - lseB);
+      float mbA, mbB;
+      if constexpr (SEG) {
+        mbA = sk_r[r] == sqA ? 0.f : FA_SEG_BIAS;
+        mbB = sk_r[r] == sqB ? 0.f : FA_SEG_BIAS;
+      } else {
+        mbA = mbB = mb_r[r];
+      }
+      float expA = __expf(sA[r] * scale + mbA - lseA);
+      float expB = __expf(sB[r] * scale + mbB - lseB);
       gA[r] = scale * expA * (pA[r] - ddA);
       gB[r] = scale * expB * (pB[r] - ddB);
     }
@@ -954,30 +1133,46 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   }
 }
 
+static void fa_dq_recompute_dispatch(const short* q, const short* k,
+                                     const short* v, const void* dout,
+                                     const void* mask, const void* seg,
+                                     const void* lse, const void* ddot,
+                                     void* dq, int B, int H, int L,
+                                     float scale, FaGeom g,
+                                     hipStream_t stream) {
+  const dim3 grid = fa_grid(B, H, L, FA_Q2WG);
+  if (seg)
+    flash_dq_recompute_kernel<true><<<grid, FA_BLOCK, DQR_LDS_BYTES,
+                                      stream>>>(
+        q, k, v, (const short*)dout, nullptr, (const int*)seg,
+        (const float*)lse, (const float*)ddot, (short*)dq, B, H, L, scale, g);
+  else
+    flash_dq_recompute_kernel<false><<<grid, FA_BLOCK, DQR_LDS_BYTES,
+                                       stream>>>(
+        q, k, v, (const short*)dout, (const float*)mask, nullptr,
+        (const float*)lse, (const float*)ddot, (short*)dq, B, H, L, scale, g);
+}
+
 extern "C" hipError_t flash_dq_recompute_launch(
     const void* q, const void* k, const void* v, const void* dout,
-    const void* mask, const void* lse, const void* ddot, void* dq,
-    int B, int H, int L, float scale, hipStream_t stream) {
-  flash_dq_recompute_kernel<<<fa_grid(B, H, L, FA_Q2WG), FA_BLOCK,
-                              DQR_LDS_BYTES, stream>>>(
-      (const short*)q, (const short*)k, (const short*)v, (const short*)dout,
-      (const float*)mask, (const float*)lse, (const float*)ddot, (short*)dq,
-      B, H, L, scale, FaGeom::bhld(H, L));
+    const void* mask, const void* seg, const void* lse, const void* ddot,
+    void* dq, int B, int H, int L, float scale, hipStream_t stream) {
+  fa_dq_recompute_dispatch((const short*)q, (const short*)k, (const short*)v,
+                           dout, mask, seg, lse, ddot, dq, B, H, L, scale,
+                           FaGeom::bhld(H, L), stream);
   return hipGetLastError();
 }
 
 // packed: dq lands in the q third of dqkv [B, L, 3D]
 extern "C" hipError_t flash_dq_recompute_packed_launch(
-    const void* qkv, const void* dout, const void* mask, const void* lse,
-    const void* ddot, void* dqkv, int B, int H, int L, float scale,
-    hipStream_t stream) {
+    const void* qkv, const void* dout, const void* mask, const void* seg,
+    const void* lse, const void* ddot, void* dqkv, int B, int H, int L,
+    float scale, hipStream_t stream) {
   const int D = H * FA_DH;
-  flash_dq_recompute_kernel<<<fa_grid(B, H, L, FA_Q2WG), FA_BLOCK,
-                              DQR_LDS_BYTES, stream>>>(
-      (const short*)qkv, (const short*)qkv + D, (const short*)qkv + 2 * D,
-      (const short*)dout, (const float*)mask, (const float*)lse,
-      (const float*)ddot, (short*)dqkv,
-      B, H, L, scale, FaGeom::packed(H, L));
+  fa_dq_recompute_dispatch((const short*)qkv, (const short*)qkv + D,
+                           (const short*)qkv + 2 * D, dout, mask, seg, lse,
+                           ddot, dqkv, B, H, L, scale, FaGeom::packed(H, L),
+                           stream);
   return hipGetLastError();
 }
 

@@ -36,36 +36,43 @@ hipError_t out_repack_launch(const void*, void*, int, int, int, int, int,
 hipError_t qkv_repack_bwd3_launch(const void*, const void*, const void*,
                                   void*, int, int, int, int, hipStream_t);
 hipError_t flash_fwd_launch(const void*, const void*, const void*, const void*,
-                            void*, void*, int, int, int, float, hipStream_t);
+                            const void*, void*, void*, int, int, int, float,
+                            hipStream_t);
 hipError_t p_from_lse_launch(const void*, const void*, const void*, void*,
                              long, int, int, float, int, hipStream_t);
 hipError_t flash_bwd_fused_launch(const void*, const void*, const void*,
                                   const void*, const void*, const void*,
-                                  const void*, void*, void*, void*, int, int,
-                                  int, float, hipStream_t);
+                                  const void*, const void*, void*, void*,
+                                  void*, int, int, int, float, hipStream_t);
 hipError_t fa_dot_launch(const void*, const void*, void*, long, hipStream_t);
 hipError_t fa_dot_packed_launch(const void*, const void*, void*, int, int,
                                 int, hipStream_t);
-hipError_t flash_fwd_packed_launch(const void*, const void*, void*, void*,
-                                   int, int, int, float, hipStream_t);
+hipError_t flash_fwd_packed_launch(const void*, const void*, const void*,
+                                   void*, void*, int, int, int, float,
+                                   hipStream_t);
 hipError_t flash_bwd_fused_packed_launch(const void*, const void*,
                                          const void*, const void*,
-                                         const void*, void*, int, int, int,
-                                         float, hipStream_t);
+                                         const void*, const void*, void*,
+                                         int, int, int, float, hipStream_t);
 hipError_t flash_dq_recompute_packed_launch(const void*, const void*,
                                             const void*, const void*,
-                                            const void*, void*, int, int,
-                                            int, float, hipStream_t);
+                                            const void*, const void*, void*,
+                                            int, int, int, float,
+                                            hipStream_t);
 hipError_t flash_dq_recompute_launch(const void*, const void*, const void*,
                                      const void*, const void*, const void*,
-                                     const void*, void*, int, int, int, float,
-                                     hipStream_t);
+                                     const void*, const void*, void*, int,
+                                     int, int, float, hipStream_t);
 hipError_t flash_dq_launch(const void*, const void*, void*, int, int, int,
                            hipStream_t);
 hipError_t masked_pool_fwd_launch(const void*, const void*, void*, void*,
                                   void*, int, int, int, hipStream_t);
 hipError_t masked_pool_bwd_launch(const void*, const void*, const void*,
                                   void*, int, int, int, hipStream_t);
+hipError_t segment_pool_fwd_launch(const void*, const void*, const void*,
+                                   void*, int, long, int, hipStream_t);
+hipError_t segment_pool_bwd_launch(const void*, const void*, const void*,
+                                   void*, int, long, int, hipStream_t);
 hipError_t tr_probe_launch(const void*, void*, int, hipStream_t);
 hipError_t colsum_bf16_launch(const void*, void*, void*, long, int,
                               hipStream_t);
@@ -117,6 +124,32 @@ const void* flash_mask_ptr(const c10::optional<torch::Tensor>& mask,
   TORCH_CHECK(mask->dim() == 2 && mask->size(0) == d.B &&
               mask->size(1) == d.L, "mask must be [B, L]");
   return mask->data_ptr();
+}
+
+// Optional segment ids (sequence packing): int32, contiguous, on x's device,
+// exactly [B, L]; exclusive with mask.  Row-wise monotonicity is the
+// caller's contract (checking it would need a device sync): a row that
+// breaks it gives wrong numbers, never an out-of-bounds access.
+const void* flash_seg_ptr(const c10::optional<torch::Tensor>& seg,
+                          const c10::optional<torch::Tensor>& mask,
+                          const torch::Tensor& x, const FlashDims& d) {
+  if (!seg.has_value()) return nullptr;
+  TORCH_CHECK(!mask.has_value(), "mask and seg are mutually exclusive");
+  TORCH_CHECK(seg->scalar_type() == torch::kInt32, "seg must be int32");
+  TORCH_CHECK(seg->device() == x.device(), "seg must be on the same device "
+              "as the attention inputs");
+  TORCH_CHECK(seg->is_contiguous(), "seg must be contiguous");
+  TORCH_CHECK(seg->dim() == 2 && seg->size(0) == d.B && seg->size(1) == d.L,
+              "seg must be [B, L]");
+  return seg->data_ptr();
+}
+
+void check_i32(const torch::Tensor& t, const torch::Tensor& like,
+               const char* name) {
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be int32");
+  TORCH_CHECK(t.device() == like.device(), name, " must be on the same "
+              "device as the data");
 }
 
 // Per-row f32 statistics (lse, ddot): [B, H, L].
@@ -397,14 +430,16 @@ torch::Tensor out_repack_bwd(torch::Tensor dgrad, long H) {
 std::vector<torch::Tensor> flash_fwd(torch::Tensor q, torch::Tensor k,
                                      torch::Tensor v,
                                      c10::optional<torch::Tensor> mask,
-                                     double scale) {
+                                     double scale,
+                                     c10::optional<torch::Tensor> seg) {
   const auto [B, H, L] = check_flash_bhld("q", q, {{"k", k}, {"v", v}}, {});
   const void* mptr = flash_mask_ptr(mask, {B, H, L});
+  const void* sptr = flash_seg_ptr(seg, mask, q, {B, H, L});
   auto o = torch::empty_like(q);
   auto lse = torch::empty({B, H, L}, q.options().dtype(torch::kFloat32));
   CHECK_HIP(flash_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), mptr,
-                             o.data_ptr(), lse.data_ptr(), (int)B, (int)H,
-                             (int)L, (float)scale, cur_stream()));
+                             sptr, o.data_ptr(), lse.data_ptr(), (int)B,
+                             (int)H, (int)L, (float)scale, cur_stream()));
   return {o, lse};
 }
 
@@ -446,11 +481,15 @@ std::vector<torch::Tensor> flash_bwd_fused(torch::Tensor q, torch::Tensor k,
                                            c10::optional<torch::Tensor> mask,
                                            torch::Tensor lse,
                                            torch::Tensor ddot, double scale,
-                                           bool emit_ds) {
+                                           bool emit_ds,
+                                           c10::optional<torch::Tensor> seg) {
   const auto [B, H, L] = check_flash_bhld(
       "q", q, {{"k", k}, {"v", v}, {"dout", dout}},
       {{"lse", lse}, {"ddot", ddot}});
   const void* mptr = flash_mask_ptr(mask, {B, H, L});
+  const void* sptr = flash_seg_ptr(seg, mask, q, {B, H, L});
+  TORCH_CHECK(!(sptr && emit_ds), "seg with emit_ds=True is not supported: "
+              "the flash_dq A/B path is unsegmented");
   // emit_ds=false (the default): no [B, H, L, L] dS materialization — dQ
   // comes from flash_dq_recompute instead.
   auto dk = torch::empty_like(k);
@@ -462,8 +501,8 @@ std::vector<torch::Tensor> flash_bwd_fused(torch::Tensor q, torch::Tensor k,
     ds_ptr = ds.data_ptr();
   }
   CHECK_HIP(flash_bwd_fused_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                   dout.data_ptr(), mptr, lse.data_ptr(),
-                                   ddot.data_ptr(), ds_ptr,
+                                   dout.data_ptr(), mptr, sptr,
+                                   lse.data_ptr(), ddot.data_ptr(), ds_ptr,
                                    dk.data_ptr(), dv.data_ptr(), (int)B,
                                    (int)H, (int)L, (float)scale,
                                    cur_stream()));
@@ -510,14 +549,16 @@ torch::Tensor bias_grad(torch::Tensor dy) {
 
 std::vector<torch::Tensor> flash_fwd_packed(torch::Tensor qkv, long H,
                                             c10::optional<torch::Tensor> mask,
-                                            double scale) {
+                                            double scale,
+                                            c10::optional<torch::Tensor> seg) {
   // qkv: [B, L, 3D] packed projection output, D = H*64
   const auto dims = check_flash_packed(qkv, H, {}, {});
   const long B = dims.B, L = dims.L;
   const void* mptr = flash_mask_ptr(mask, dims);
+  const void* sptr = flash_seg_ptr(seg, mask, qkv, dims);
   auto o = torch::empty({B, L, H * 64}, qkv.options());
   auto lse = torch::empty({B, H, L}, qkv.options().dtype(torch::kFloat32));
-  CHECK_HIP(flash_fwd_packed_launch(qkv.data_ptr(), mptr, o.data_ptr(),
+  CHECK_HIP(flash_fwd_packed_launch(qkv.data_ptr(), mptr, sptr, o.data_ptr(),
                                     lse.data_ptr(), (int)B, (int)H, (int)L,
                                     (float)scale, cur_stream()));
   return {o, lse};
@@ -526,23 +567,27 @@ std::vector<torch::Tensor> flash_fwd_packed(torch::Tensor qkv, long H,
 torch::Tensor flash_bwd_packed(torch::Tensor qkv, torch::Tensor o,
                                torch::Tensor dout,
                                c10::optional<torch::Tensor> mask,
-                               torch::Tensor lse, long H, double scale) {
+                               torch::Tensor lse, long H, double scale,
+                               c10::optional<torch::Tensor> seg) {
   // full packed backward: ddot + dK/dV + dQ, all into one [B, L, 3D] grad
   const auto dims = check_flash_packed(qkv, H, {{"o", o}, {"dout", dout}},
                                        {{"lse", lse}});
   const long B = dims.B, L = dims.L;
   const void* mptr = flash_mask_ptr(mask, dims);
+  const void* sptr = flash_seg_ptr(seg, mask, qkv, dims);
   auto ddot = torch::empty({B, H, L}, qkv.options().dtype(torch::kFloat32));
   CHECK_HIP(fa_dot_packed_launch(dout.data_ptr(), o.data_ptr(),
                                  ddot.data_ptr(), (int)B, (int)H, (int)L,
                                  cur_stream()));
   auto dqkv = torch::empty_like(qkv);
   CHECK_HIP(flash_bwd_fused_packed_launch(
-      qkv.data_ptr(), dout.data_ptr(), mptr, lse.data_ptr(), ddot.data_ptr(),
-      dqkv.data_ptr(), (int)B, (int)H, (int)L, (float)scale, cur_stream()));
+      qkv.data_ptr(), dout.data_ptr(), mptr, sptr, lse.data_ptr(),
+      ddot.data_ptr(), dqkv.data_ptr(), (int)B, (int)H, (int)L, (float)scale,
+      cur_stream()));
   CHECK_HIP(flash_dq_recompute_packed_launch(
-      qkv.data_ptr(), dout.data_ptr(), mptr, lse.data_ptr(), ddot.data_ptr(),
-      dqkv.data_ptr(), (int)B, (int)H, (int)L, (float)scale, cur_stream()));
+      qkv.data_ptr(), dout.data_ptr(), mptr, sptr, lse.data_ptr(),
+      ddot.data_ptr(), dqkv.data_ptr(), (int)B, (int)H, (int)L, (float)scale,
+      cur_stream()));
   return dqkv;
 }
 
@@ -550,15 +595,17 @@ torch::Tensor flash_dq_recompute(torch::Tensor q, torch::Tensor k,
                                  torch::Tensor v, torch::Tensor dout,
                                  c10::optional<torch::Tensor> mask,
                                  torch::Tensor lse, torch::Tensor ddot,
-                                 double scale) {
+                                 double scale,
+                                 c10::optional<torch::Tensor> seg) {
   const auto [B, H, L] = check_flash_bhld(
       "q", q, {{"k", k}, {"v", v}, {"dout", dout}},
       {{"lse", lse}, {"ddot", ddot}});
   const void* mptr = flash_mask_ptr(mask, {B, H, L});
+  const void* sptr = flash_seg_ptr(seg, mask, q, {B, H, L});
   auto dq = torch::empty_like(q);
   CHECK_HIP(flash_dq_recompute_launch(q.data_ptr(), k.data_ptr(),
                                       v.data_ptr(), dout.data_ptr(), mptr,
-                                      lse.data_ptr(), ddot.data_ptr(),
+                                      sptr, lse.data_ptr(), ddot.data_ptr(),
                                       dq.data_ptr(), (int)B, (int)H, (int)L,
                                       (float)scale, cur_stream()));
   return dq;
@@ -610,6 +657,48 @@ torch::Tensor masked_pool_bwd(torch::Tensor dpooled,
   return dx;
 }
 
+// x [T, D] bf16 (T = the packed batch's flattened positions); seg_start /
+// seg_len [N] int32 -> pooled [N, D]
+torch::Tensor segment_pool_fwd(torch::Tensor x, torch::Tensor seg_start,
+                               torch::Tensor seg_len) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be [T, D]");
+  const long T = x.size(0), D = x.size(1);
+  TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8");
+  check_i32(seg_start, x, "seg_start");
+  check_i32(seg_len, x, "seg_len");
+  TORCH_CHECK(seg_start.dim() == 1 && seg_len.dim() == 1 &&
+              seg_start.size(0) == seg_len.size(0),
+              "seg_start and seg_len must both be [N]");
+  const long N = seg_start.size(0);
+  auto pooled = torch::empty({N, D}, x.options());
+  CHECK_HIP(segment_pool_fwd_launch(x.data_ptr(), seg_start.data_ptr(),
+                                    seg_len.data_ptr(), pooled.data_ptr(),
+                                    (int)N, T, (int)D, cur_stream()));
+  return pooled;
+}
+
+// dpooled [N, D] bf16, pos2seg [T] int32 (-1 = padding), seg_len [N] int32
+// -> dx [T, D]
+torch::Tensor segment_pool_bwd(torch::Tensor dpooled, torch::Tensor pos2seg,
+                               torch::Tensor seg_len, long T) {
+  check_bf16(dpooled, "dpooled");
+  TORCH_CHECK(dpooled.dim() == 2, "dpooled must be [N, D]");
+  const long N = dpooled.size(0), D = dpooled.size(1);
+  TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8");
+  check_i32(pos2seg, dpooled, "pos2seg");
+  check_i32(seg_len, dpooled, "seg_len");
+  TORCH_CHECK(pos2seg.dim() == 1 && pos2seg.size(0) == T,
+              "pos2seg must be [T]");
+  TORCH_CHECK(seg_len.dim() == 1 && seg_len.size(0) == N,
+              "seg_len must be [N]");
+  auto dx = torch::empty({T, D}, dpooled.options());
+  CHECK_HIP(segment_pool_bwd_launch(dpooled.data_ptr(), pos2seg.data_ptr(),
+                                    seg_len.data_ptr(), dx.data_ptr(), (int)N,
+                                    T, (int)D, cur_stream()));
+  return dx;
+}
+
 torch::Tensor tr_probe(torch::Tensor src, long scheme) {
   check_bf16(src, "src");
   TORCH_CHECK(src.numel() == 256);
@@ -623,21 +712,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tr_probe", &tr_probe, "ds_read_b64_tr_b16 semantics probe");
   m.def("masked_pool_fwd", &masked_pool_fwd, "masked mean-pool fwd");
   m.def("masked_pool_bwd", &masked_pool_bwd, "masked mean-pool bwd");
-  m.def("flash_fwd", &flash_fwd, "flash attention fwd (gfx950 MFMA, dh=64)");
+  m.def("segment_pool_fwd", &segment_pool_fwd,
+        "per-segment mean-pool fwd (sequence packing)");
+  m.def("segment_pool_bwd", &segment_pool_bwd,
+        "per-segment mean-pool bwd (sequence packing)");
+  m.def("flash_fwd", &flash_fwd,
+        "flash attention fwd (gfx950 MFMA, dh=64); seg: optional int32 "
+        "[B, L] non-decreasing segment ids, exclusive with mask",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("mask"),
+        py::arg("scale"), py::arg("seg") = py::none());
   m.def("flash_bwd_fused", &flash_bwd_fused,
         "fused flash bwd: register-accumulated dK/dV (+ optional dS)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"),
         py::arg("mask"), py::arg("lse"), py::arg("ddot"), py::arg("scale"),
-        py::arg("emit_ds") = false);
+        py::arg("emit_ds") = false, py::arg("seg") = py::none());
   m.def("flash_dq_recompute", &flash_dq_recompute,
-        "dQ by recompute: S/dP/dS in-register, no dS materialization");
+        "dQ by recompute: S/dP/dS in-register, no dS materialization",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"),
+        py::arg("mask"), py::arg("lse"), py::arg("ddot"), py::arg("scale"),
+        py::arg("seg") = py::none());
   m.def("wgrad_gemm", &wgrad_gemm,
         "split-K wgrad GEMM: dW = dy^T @ x (custom MFMA)",
         py::arg("dy"), py::arg("x"), py::arg("splits") = 0);
   m.def("flash_fwd_packed", &flash_fwd_packed,
-        "flash fwd on the packed [B,L,3D] QKV projection output");
+        "flash fwd on the packed [B,L,3D] QKV projection output",
+        py::arg("qkv"), py::arg("H"), py::arg("mask"), py::arg("scale"),
+        py::arg("seg") = py::none());
   m.def("flash_bwd_packed", &flash_bwd_packed,
-        "full packed flash bwd: ddot + dK/dV + dQ into one [B,L,3D] grad");
+        "full packed flash bwd: ddot + dK/dV + dQ into one [B,L,3D] grad",
+        py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("mask"),
+        py::arg("lse"), py::arg("H"), py::arg("scale"),
+        py::arg("seg") = py::none());
   m.def("fa_dot", &fa_dot, "rowsum(dO*O) per attention row");
   m.def("flash_dq", &flash_dq, "dQ = dS @ K (MFMA, tr_b16 K^T fragments)");
   m.def("bias_grad", &bias_grad, "bf16 column-sum for linear bias grads");

@@ -20,31 +20,53 @@ from tosem2021_amd.models.tokenizer import CodeTokenizer
 from tosem2021_amd.train import TrainConfig, Trainer
 
 
+def _row_len(seq: int) -> int:
+    """Row length of a packed batch: seq rounded up to the flash kernels'
+    64-token granularity."""
+    return (seq + 63) // 64 * 64
+
+
+def _eval_batches(ds: TaxonomyDataset, tok: CodeTokenizer, batch: int,
+                  seq: int, device, pack: bool):
+    """Unshuffled (model inputs, labels, to_input_order) triples.  Packed,
+    the logits and labels are in segment order and to_input_order puts a
+    per-example tensor back into dataset order."""
+    if pack:
+        for pb, labels in ds.packed_batches(tok, batch, seq, _row_len(seq),
+                                            device=device, shuffle=False):
+            yield (pb.tokens, None, pb), labels, pb.unpermute
+    else:
+        for toks, mask, labels in ds.batches(tok, batch, seq, device=device,
+                                             shuffle=False):
+            yield (toks, mask, None), labels, (lambda x: x)
+
+
 @torch.no_grad()
 def _head_probs(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
-                seq: int, batch: int = 64):
-    """Collect sigmoid probabilities and gold multi-hot labels per head."""
+                seq: int, batch: int = 64, pack: bool = False):
+    """Collect sigmoid probabilities and gold multi-hot labels per head,
+    in dataset order (also when `pack` runs the model on packed batches)."""
     model = trainer.model
     model.eval()
     device = trainer.device
     probs = {"strategy": [], "property": []}
     gold = {"strategy": [], "property": []}
-    for toks, mask, labels in ds.batches(tok, batch, seq, device=device,
-                                         shuffle=False):
-        logits = model(toks, mask)
+    for inputs, labels, reorder in _eval_batches(ds, tok, batch, seq, device,
+                                                 pack):
+        logits = model(*inputs)
         for h in probs:
-            probs[h].append(torch.sigmoid(logits[h].float()).cpu())
-            gold[h].append(labels[h].cpu())
+            probs[h].append(reorder(torch.sigmoid(logits[h].float())).cpu())
+            gold[h].append(reorder(labels[h]).cpu())
     model.train()
     return ({h: torch.cat(v) for h, v in probs.items()},
             {h: torch.cat(v) for h, v in gold.items()})
 
 
 def tune_thresholds(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
-                    seq: int) -> Dict[str, torch.Tensor]:
+                    seq: int, pack: bool = False) -> Dict[str, torch.Tensor]:
     """Per-class decision thresholds maximizing F1 on `ds` (use the TRAIN
     split here; evaluate() then reports on the held-out split)."""
-    probs, gold = _head_probs(trainer, ds, tok, seq)
+    probs, gold = _head_probs(trainer, ds, tok, seq, pack=pack)
     grid = torch.arange(0.05, 0.95, 0.05)
     out = {}
     for h in probs:
@@ -68,8 +90,8 @@ def tune_thresholds(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
 @torch.no_grad()
 def evaluate(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
              seq: int, batch: int = 64, threshold: float = 0.5,
-             thresholds: Optional[Dict[str, torch.Tensor]] = None
-             ) -> Dict[str, float]:
+             thresholds: Optional[Dict[str, torch.Tensor]] = None,
+             pack: bool = False) -> Dict[str, float]:
     model = trainer.model
     model.eval()
     device = trainer.device
@@ -77,9 +99,11 @@ def evaluate(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
     prop_scores = {l: LabelScore(l) for l in PROPERTIES}
     method_hits = 0
     n = 0
-    for toks, mask, labels in ds.batches(tok, batch, seq, device=device,
-                                         shuffle=False):
-        logits = model(toks, mask)
+    for inputs, labels, _ in _eval_batches(ds, tok, batch, seq, device,
+                                           pack):
+        # packed, logits and labels share the segment order; the counts
+        # below do not depend on the order
+        logits = model(*inputs)
         th_s = thresholds["strategy"].to(device) if thresholds else threshold
         th_p = thresholds["property"].to(device) if thresholds else threshold
         sp = (torch.sigmoid(logits["strategy"].float()) > th_s)
@@ -98,7 +122,7 @@ def evaluate(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
             s.fp += int((pp[:, i] & ~gp[:, i]).sum())
             s.fn += int((~pp[:, i] & gp[:, i]).sum())
         method_hits += int((mp == labels["method"]).sum())
-        n += toks.shape[0]
+        n += labels["method"].shape[0]
     model.train()
     return {
         "strategy_micro_f1": micro_f1(strat_scores),
@@ -129,7 +153,8 @@ def _load_dataset(taxonomy_path: str, cfg: MLTCConfig) -> TaxonomyDataset:
 def _run_steps(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
                batch: int, seq: int, steps: int, seed: int, device,
                eval_every: int = 0, val_ds: Optional[TaxonomyDataset] = None,
-               tag: str = "", augment: float = 0.0) -> list:
+               tag: str = "", augment: float = 0.0,
+               pack: bool = False) -> list:
     losses = []
     epoch = 0
     it = iter(())
@@ -142,18 +167,28 @@ def _run_steps(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
         try:
             toks, mask, labels = next(it)
         except StopIteration:
-            it = ds.batches(tok, batch, seq, device=device, shuffle=True,
-                            seed=seed + epoch, drop_last=True)
+            if pack:
+                # (PackedBatch, None, labels in segment order)
+                it = ((pb, None, lab) for pb, lab in ds.packed_batches(
+                    tok, batch, seq, _row_len(seq), device=device,
+                    shuffle=True, seed=seed + epoch, drop_last=True))
+            else:
+                it = ds.batches(tok, batch, seq, device=device, shuffle=True,
+                                seed=seed + epoch, drop_last=True)
             epoch += 1
             continue
         if augment > 0:
             from tosem2021_amd.data.augment import augment_tokens
-            toks = augment_tokens(toks, augment, aug_keep,
-                                  tok.vocab_size, aug_gen)
+            if pack:
+                toks.tokens = augment_tokens(toks.tokens, augment, aug_keep,
+                                             tok.vocab_size, aug_gen)
+            else:
+                toks = augment_tokens(toks, augment, aug_keep,
+                                      tok.vocab_size, aug_gen)
         losses.append(trainer.step(toks, mask, labels))
         if eval_every and val_ds is not None and \
                 trainer.step_num % eval_every == 0:
-            ev = evaluate(trainer, val_ds, tok, seq)
+            ev = evaluate(trainer, val_ds, tok, seq, pack=pack)
             print(f"{tag}step {trainer.step_num} loss {losses[-1]:.4f} "
                   f"strategyF1 {ev['strategy_micro_f1']:.3f} "
                   f"propF1 {ev['property_micro_f1']:.3f} "
@@ -173,8 +208,13 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                      label_smoothing: float = 0.0,
                      dump_probs_path: Optional[str] = None,
                      augment: float = 0.0,
-                     split_seed: Optional[int] = None) -> dict:
+                     split_seed: Optional[int] = None,
+                     pack: bool = False) -> dict:
     """Fine-tune MLTC on `taxonomy_path`'s labeled rows.
+
+    `pack` trains and evaluates on packed batches (data.packing): each
+    step's `batch` examples share rows of `seq` tokens instead of one padded
+    row each.
 
     With `pretrain_path`/`pretrain_steps`, first train on that (typically
     mined, rule-labeled) taxonomy, then warm-start the fine-tune from the
@@ -220,7 +260,7 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
         pre_tr.model.set_pos_weights(
             {k: v.to(dev) for k, v in pre_ds.pos_weights().items()})
         _run_steps(pre_tr, pre_ds, tok, batch, seq, pretrain_steps, seed,
-                   dev, eval_every, val_ds, tag="pre ")[0]
+                   dev, eval_every, val_ds, tag="pre ", pack=pack)[0]
         # warm-start: pretrained weights, fresh optimizer state + schedule
         trainer.flat.flat.copy_(pre_tr.flat.flat)
         trainer.flat.master.copy_(pre_tr.flat.master)
@@ -229,21 +269,21 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
 
     losses, epoch = _run_steps(trainer, train_ds, tok, batch, seq, steps,
                                seed, dev, eval_every, val_ds,
-                               augment=augment)
+                               augment=augment, pack=pack)
     train_time = time.time() - t0
-    ev = evaluate(trainer, val_ds, tok, seq)
-    ev_lo = evaluate(trainer, val_ds, tok, seq, threshold=0.3)
+    ev = evaluate(trainer, val_ds, tok, seq, pack=pack)
+    ev_lo = evaluate(trainer, val_ds, tok, seq, threshold=0.3, pack=pack)
     ev["strategy_micro_f1_t0.3"] = ev_lo["strategy_micro_f1"]
     ev["property_micro_f1_t0.3"] = ev_lo["property_micro_f1"]
-    ths = tune_thresholds(trainer, train_ds, tok, seq)
-    ev_tuned = evaluate(trainer, val_ds, tok, seq, thresholds=ths)
+    ths = tune_thresholds(trainer, train_ds, tok, seq, pack=pack)
+    ev_tuned = evaluate(trainer, val_ds, tok, seq, thresholds=ths, pack=pack)
     ev["strategy_micro_f1_tuned"] = round(ev_tuned["strategy_micro_f1"], 4)
     ev["property_micro_f1_tuned"] = round(ev_tuned["property_micro_f1"], 4)
     if dump_probs_path:
         # sigmoid probs + gold for the val AND train splits — enables
         # offline ensembling/blending without the GPU
-        vp, vg = _head_probs(trainer, val_ds, tok, seq)
-        tp_, tg = _head_probs(trainer, train_ds, tok, seq)
+        vp, vg = _head_probs(trainer, val_ds, tok, seq, pack=pack)
+        tp_, tg = _head_probs(trainer, train_ds, tok, seq, pack=pack)
         torch.save({"val_probs": vp, "val_gold": vg,
                     "train_probs": tp_, "train_gold": tg,
                     "seed": seed}, dump_probs_path)
@@ -268,9 +308,11 @@ def apply_classifier(ckpt_dir: str, taxonomy_path: str, out_csv: str,
                      model: str = "mltc-base", seq: int = 256,
                      batch: int = 64, threshold: float = 0.5,
                      device: Optional[str] = None,
-                     repo_prefix: bool = False) -> str:
+                     repo_prefix: bool = False, pack: bool = False) -> str:
     """Label the rows of a (mined) taxonomy CSV with a trained MLTC model and
-    rewrite the 41-column CSV with the predicted labels."""
+    rewrite the 41-column CSV with the predicted labels.  `pack` runs each
+    chunk of `batch` texts as one packed batch; the rows come out in input
+    order either way."""
     from tosem2021_amd.extract.schema import (
         METHODS, PROPERTIES, STAGES, STRATEGIES, STRATEGY_TO_COLUMNS,
         TestCaseRow)
@@ -299,8 +341,13 @@ def apply_classifier(ckpt_dir: str, taxonomy_path: str, out_csv: str,
     rows = []
     for lo in range(0, len(texts), batch):
         chunk = texts[lo:lo + batch]
-        toks, mask = tok.encode_batch(chunk, seq, device=dev)
-        logits = trainer.model(toks, mask)
+        if pack:
+            pb = tok.encode_packed(chunk, seq, _row_len(seq), device=dev)
+            logits = {h: pb.unpermute(v) for h, v in
+                      trainer.model(pb.tokens, packing=pb).items()}
+        else:
+            toks, mask = tok.encode_batch(chunk, seq, device=dev)
+            logits = trainer.model(toks, mask)
         sp = torch.sigmoid(logits["strategy"].float()) > threshold
         pp = torch.sigmoid(logits["property"].float()) > threshold
         stg = logits["stage"].float().argmax(-1)

@@ -128,7 +128,7 @@ def cmd_classify(args):
     out = apply_classifier(args.ckpt_dir, args.taxonomy, args.out,
                            model=args.model, seq=args.seq,
                            threshold=args.threshold,
-                           repo_prefix=args.repo_prefix)
+                           repo_prefix=args.repo_prefix, pack=args.pack)
     print(f"wrote {out}")
 
 
@@ -142,7 +142,7 @@ def cmd_train(args):
         focal_gamma_property=args.focal_gamma_property,
         label_smoothing=args.label_smoothing, eval_every=args.eval_every,
         seed=args.seed, dump_probs_path=args.dump_probs,
-        augment=args.augment, split_seed=args.split_seed)
+        augment=args.augment, split_seed=args.split_seed, pack=args.pack)
     print(json.dumps(res, indent=2))
 
 
@@ -212,6 +212,9 @@ def main(argv=None):
     p.add_argument("--threshold", type=float, default=0.5)
     p.add_argument("--repo-prefix", action="store_true",
                    help="model was trained on repo-prefixed text")
+    p.add_argument("--pack", action="store_true",
+                   help="pack several texts per row instead of padding "
+                        "each to its own row")
     p.set_defaults(fn=cmd_classify)
 
     p = sub.add_parser("train", help="train the MLTC classifier on a taxonomy")
@@ -240,6 +243,9 @@ def main(argv=None):
     p.add_argument("--dump-probs", default=None,
                    help="save val/train sigmoid probs + gold for offline "
                         "ensembling")
+    p.add_argument("--pack", action="store_true",
+                   help="train and evaluate on packed batches (several "
+                        "examples per row, segment-aware attention)")
     p.set_defaults(fn=cmd_train)
 
     args = ap.parse_args(argv)

@@ -134,3 +134,39 @@ class TaxonomyDataset:
                 "method": self.method[ix].to(device),
             }
             yield toks, mask, labels
+
+    def packed_batches(self, tokenizer: CodeTokenizer, batch_size: int,
+                       max_len: int, row_len: int, device="cpu",
+                       shuffle: bool = True, seed: int = 0,
+                       drop_last: bool = False):
+        """Like batches(), but each group of `batch_size` examples is packed
+        into rows of `row_len` tokens (data.packing).  Yields
+        (PackedBatch, labels) with the labels already gathered into the
+        batch's segment order, so they line up with the model's packed
+        logits; PackedBatch.order maps segments back to the group."""
+        from tosem2021_amd.data.packing import pack_examples
+        from tosem2021_amd.models.tokenizer import PAD
+        n = len(self)
+        g = torch.Generator().manual_seed(seed)
+        order = torch.randperm(n, generator=g) if shuffle else torch.arange(n)
+        cap = min(max_len, row_len)
+        for lo in range(0, n, batch_size):
+            ix = order[lo:lo + batch_size]
+            if drop_last and len(ix) < batch_size:
+                break
+            if self._tokens is not None:
+                toks = self._tokens[ix, :cap]
+                mask = self._mask[ix, :cap]
+                rows = [t[m].tolist() for t, m in zip(toks, mask)]
+            else:
+                rows = [tokenizer.encode(self.texts[i], cap)
+                        for i in ix.tolist()]
+            pb = pack_examples(rows, row_len, pad_id=PAD)
+            sel = ix[pb.order]
+            labels = {
+                "strategy": self.strategy[sel].to(device),
+                "property": self.property_[sel].to(device),
+                "stage": self.stage[sel].to(device),
+                "method": self.method[sel].to(device),
+            }
+            yield pb.to(device), labels

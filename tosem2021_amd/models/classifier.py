@@ -125,7 +125,10 @@ class Attention(nn.Module):
         self.qkv = nn.Linear(cfg.d_model, 3 * cfg.d_model, bias=True)
         self.proj = nn.Linear(cfg.d_model, cfg.d_model, bias=True)
 
-    def forward(self, x, mask_bias: Optional[torch.Tensor]):
+    def forward(self, x, mask_bias: Optional[torch.Tensor],
+                seg: Optional[torch.Tensor] = None):
+        """seg: [B, L] int32 segment ids of a packed batch (exclusive with
+        mask_bias): attention stays inside each segment."""
         B, L, D = x.shape
         if ops.flash_supported(self.head_dim, L):
             # MFMA flash kernels run straight on the packed [B, L, 3D]
@@ -133,8 +136,22 @@ class Attention(nn.Module):
             # every gradient) in the packed layouts — no repack kernels,
             # no [L, L] score tensor, O(L) attention memory
             out = ops.flash_attention_packed(_linear(self.qkv, x), self.n_heads,
-                                             mask_bias, self.scale)
+                                             mask_bias, self.scale, seg)
             return _linear(self.proj, out)
+        if seg is not None:
+            if x.is_cuda:
+                # no O(L^2) fallback: packing exists to cut attention work
+                raise RuntimeError(
+                    "sequence packing on the GPU needs the segment-aware "
+                    f"flash kernels: head_dim 64 and L % 32 == 0, got "
+                    f"head_dim {self.head_dim}, L {L}")
+            # CPU reference for any shape: plain softmax over the
+            # segment bias
+            q, k, v = ops.qkv_repack(self.qkv(x), self.n_heads)
+            s = torch.matmul(q, k.transpose(-1, -2)).float() * self.scale
+            p = torch.softmax(s + ops.reference.segment_bias(seg), dim=-1)
+            out = torch.matmul(p.to(v.dtype), v)
+            return self.proj(ops.out_repack(out))
         # general-shape fallback: gather kernel to bmm-ready
         # [3, B, H, L, dh] (csrc/repack.hip), bmm + fused softmax
         q, k, v = ops.qkv_repack(self.qkv(x), self.n_heads)  # [B, H, L, dh]
@@ -185,7 +202,7 @@ class EncoderBlock(nn.Module):
     def _drop(self, h):
         return F.dropout(h, self.dropout, self.training) if self.dropout else h
 
-    def forward(self, x, delta, mask_bias):
+    def forward(self, x, delta, mask_bias, seg=None):
         if delta is None:
             y1 = ops.fused_layernorm(x, self.ln1.weight, self.ln1.bias,
                                      self.ln1.eps)
@@ -193,7 +210,7 @@ class EncoderBlock(nn.Module):
         else:
             y1, s1 = ops.fused_add_layernorm(x, delta, self.ln1.weight,
                                              self.ln1.bias, self.ln1.eps)
-        h = self._drop(self.attn(y1, mask_bias))
+        h = self._drop(self.attn(y1, mask_bias, seg))
         y2, s2 = ops.fused_add_layernorm(s1, h, self.ln2.weight,
                                          self.ln2.bias, self.ln2.eps)
         h2 = self._drop(self.ffn(y2))
@@ -220,9 +237,18 @@ class MLTC(nn.Module):
             if isinstance(m, nn.Linear) and m.bias is not None:
                 nn.init.zeros_(m.bias)
 
-    def forward(self, tokens: torch.Tensor,
-                attn_mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """tokens: [B, L] int64; attn_mask: [B, L] bool (True = valid)."""
+    def forward(self, tokens: Optional[torch.Tensor],
+                attn_mask: Optional[torch.Tensor] = None,
+                packing=None) -> Dict[str, torch.Tensor]:
+        """tokens: [B, L] int64; attn_mask: [B, L] bool (True = valid).
+
+        packing: a data.packing.PackedBatch (exclusive with attn_mask;
+        tokens may be None and defaults to packing.tokens).  Positions come
+        from packing.pos, attention stays inside packing.seg's segments and
+        the pool is per segment: logits are [N, .] in SEGMENT order —
+        packing.unpermute() restores the examples' input order."""
+        if packing is not None:
+            return self._forward_packed(tokens, attn_mask, packing)
         B, L = tokens.shape
         pos = torch.arange(L, device=tokens.device)
         x = self.tok_emb(tokens) + self.pos_emb(pos)[None, :, :]
@@ -241,6 +267,27 @@ class MLTC(nn.Module):
                                            self.ln_f.bias, self.ln_f.eps)
         # masked mean-pool over valid tokens (fused kernel: csrc/pool.hip)
         pooled = ops.masked_mean_pool(x, attn_mask)
+        return {name: head(pooled) for name, head in self.heads.items()}
+
+    def _forward_packed(self, tokens, attn_mask, packing):
+        if attn_mask is not None:
+            raise ValueError("attn_mask and packing are mutually exclusive: "
+                             "a packed batch carries its own padding segment")
+        if tokens is None:
+            tokens = packing.tokens
+        R, L = tokens.shape
+        x = self.tok_emb(tokens) + self.pos_emb(packing.pos)
+        delta = None
+        for blk in self.blocks:
+            x, delta = blk(x, delta, None, packing.seg)
+        if delta is None:
+            x = self.ln_f(x)
+        else:
+            x, _ = ops.fused_add_layernorm(x, delta, self.ln_f.weight,
+                                           self.ln_f.bias, self.ln_f.eps)
+        # per-example mean-pool over the flattened positions
+        pooled = ops.segment_mean_pool(x.reshape(R * L, -1), packing.seg_start,
+                                       packing.seg_len, packing.pos2seg)
         return {name: head(pooled) for name, head in self.heads.items()}
 
     def set_pos_weights(self, weights: Dict[str, torch.Tensor]) -> None:

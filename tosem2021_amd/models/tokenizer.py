@@ -70,3 +70,14 @@ class CodeTokenizer:
             toks[i, :len(r)] = torch.tensor(r, dtype=torch.long)
             mask[i, :len(r)] = True
         return toks.to(device), mask.to(device)
+
+    def encode_packed(self, texts: List[str], max_len: int, row_len: int,
+                      device="cpu"):
+        """Encode `texts` into one packed batch (data.packing.PackedBatch):
+        each text is encoded as by encode(text, max_len) and the examples
+        are laid end to end in rows of `row_len` tokens (a multiple of 64).
+        Per-example results of the model come back in segment order;
+        PackedBatch.unpermute restores the order of `texts`."""
+        from tosem2021_amd.data.packing import pack_examples
+        rows = [self.encode(t, min(max_len, row_len)) for t in texts]
+        return pack_examples(rows, row_len, pad_id=PAD).to(device)

@@ -302,44 +302,75 @@ class _FlashAttentionFn(torch.autograd.Function):
     (in-register S/dP/dS, accumulates dQ) — no [L, L] dS materialization."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, scale):
+    def forward(ctx, q, k, v, mask, scale, seg=None):
         if q.is_cuda:
-            o, lse = hip_ops().flash_fwd(q, k, v, mask, scale)
+            o, lse = hip_ops().flash_fwd(q, k, v, mask, scale, seg)
         else:
-            o, lse = reference.flash_attention_fwd(q, k, v, mask, scale)
+            bias = reference.segment_bias(seg) if seg is not None else None
+            o, lse = reference.flash_attention_fwd(q, k, v, mask, scale, bias)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.mask = mask
+        ctx.seg = seg
         ctx.scale = scale
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
-        mask, scale = ctx.mask, ctx.scale
+        mask, seg, scale = ctx.mask, ctx.seg, ctx.scale
         do = do.contiguous()
         if q.is_cuda:
             # two recompute MFMA kernels; dS never touches HBM (round 2 —
             # the round-1 pipeline wrote + re-read a [B, H, L, L] bf16 dS)
             ddot = hip_ops().fa_dot(do, o)
             dk, dv = hip_ops().flash_bwd_fused(q, k, v, do, mask, lse,
-                                               ddot, scale)
+                                               ddot, scale, False, seg)
             dq = hip_ops().flash_dq_recompute(q, k, v, do, mask, lse,
-                                              ddot, scale)
-            return dq, dk, dv, None, None
+                                              ddot, scale, seg)
+            return dq, dk, dv, None, None, None
+        bias = reference.segment_bias(seg) if seg is not None else None
         s = torch.matmul(q, k.transpose(-1, -2))
-        p = reference.p_from_lse(s, mask, lse, scale)
+        p = reference.p_from_lse(s, mask, lse, scale, bias)
         dp = torch.matmul(do, v.transpose(-1, -2))
         dsc = reference.softmax_bwd(dp, p, scale)
         dq = torch.matmul(dsc, k)
         dk = torch.matmul(dsc.transpose(-1, -2), q)
         dv = torch.matmul(p.transpose(-1, -2), do)
-        return dq, dk, dv, None, None
+        return dq, dk, dv, None, None, None
 
 
-def flash_attention(q, k, v, mask=None, scale: float = 1.0):
-    """q/k/v: [B, H, L, 64] bf16 contiguous, L % 32 == 0; mask: [B, L] f32."""
+def _check_mask_seg(mask, seg):
+    if mask is not None and seg is not None:
+        raise ValueError("mask and seg are mutually exclusive: a packed "
+                         "batch marks its padding as a trailing segment")
+
+
+def check_segments(seg: torch.Tensor) -> None:
+    """Host-side check of the segment contract: seg is an integer [B, L]
+    tensor whose rows never decrease.  Raises ValueError otherwise.  Syncs
+    when seg is on the GPU — meant for the packer and for tests."""
+    if seg.dim() != 2 or seg.dtype not in (torch.int32, torch.int64):
+        raise ValueError("seg must be an integer [B, L] tensor")
+    if seg.shape[1] > 1:
+        bad = (seg[:, 1:] < seg[:, :-1]).any(dim=1)
+        if bool(bad.any()):
+            rows = torch.nonzero(bad).flatten().tolist()
+            raise ValueError(f"seg rows {rows} are not non-decreasing")
+
+
+def flash_attention(q, k, v, mask=None, scale: float = 1.0, seg=None):
+    """q/k/v: [B, H, L, 64] bf16 contiguous, L % 32 == 0.
+
+    mask: optional [B, L] f32 additive key bias; a bias <= -1e8 is treated
+    as fully masked (its probability is exactly 0 and wholly masked tiles
+    are skipped).  seg: optional [B, L] int32 segment ids of a packed batch,
+    exclusive with mask: position i attends to j iff seg[b, i] == seg[b, j].
+    Each seg row must be non-decreasing, with the padding tail carrying one
+    id above every real id; that is the caller's contract (check_segments
+    verifies it on the host), not checked on the device."""
+    _check_mask_seg(mask, seg)
     return _FlashAttentionFn.apply(q.contiguous(), k.contiguous(),
-                                   v.contiguous(), mask, scale)
+                                   v.contiguous(), mask, scale, seg)
 
 
 class _FlashAttentionPackedFn(torch.autograd.Function):
@@ -350,19 +381,23 @@ class _FlashAttentionPackedFn(torch.autograd.Function):
     quartet (fwd gather, bwd3 merge, out fwd/bwd) from the step."""
 
     @staticmethod
-    def forward(ctx, qkv, n_heads, mask, scale):
+    def forward(ctx, qkv, n_heads, mask, scale, seg=None):
         if qkv.is_cuda:
-            o, lse = hip_ops().flash_fwd_packed(qkv, n_heads, mask, scale)
+            o, lse = hip_ops().flash_fwd_packed(qkv, n_heads, mask, scale,
+                                                seg)
         else:
             B, L, D3 = qkv.shape
             d = D3 // 3
             q, k, v = (t.view(B, L, n_heads, 64).transpose(1, 2).contiguous()
                        for t in qkv.split(d, dim=-1))
-            o4, lse = reference.flash_attention_fwd(q, k, v, mask, scale)
+            bias = reference.segment_bias(seg) if seg is not None else None
+            o4, lse = reference.flash_attention_fwd(q, k, v, mask, scale,
+                                                    bias)
             o = o4.transpose(1, 2).reshape(B, L, d)
         ctx.save_for_backward(qkv, o, lse)
         ctx.n_heads = n_heads
         ctx.mask = mask
+        ctx.seg = seg
         ctx.scale = scale
         return o
 
@@ -370,18 +405,20 @@ class _FlashAttentionPackedFn(torch.autograd.Function):
     def backward(ctx, do):
         qkv, o, lse = ctx.saved_tensors
         n_heads, mask, scale = ctx.n_heads, ctx.mask, ctx.scale
+        seg = ctx.seg
         do = do.contiguous()
         if qkv.is_cuda:
             dqkv = hip_ops().flash_bwd_packed(qkv, o, do, mask, lse,
-                                              n_heads, scale)
-            return dqkv, None, None, None
+                                              n_heads, scale, seg)
+            return dqkv, None, None, None, None
+        bias = reference.segment_bias(seg) if seg is not None else None
         B, L, D3 = qkv.shape
         d = D3 // 3
         q, k, v = (t.view(B, L, n_heads, 64).transpose(1, 2).contiguous()
                    for t in qkv.split(d, dim=-1))
         do4 = do.view(B, L, n_heads, 64).transpose(1, 2).contiguous()
         s = torch.matmul(q, k.transpose(-1, -2))
-        p = reference.p_from_lse(s, mask, lse, scale)
+        p = reference.p_from_lse(s, mask, lse, scale, bias)
         dp = torch.matmul(do4, v.transpose(-1, -2))
         dsc = reference.softmax_bwd(dp, p, scale)
         dq = torch.matmul(dsc, k)
@@ -390,14 +427,24 @@ class _FlashAttentionPackedFn(torch.autograd.Function):
         dqkv = torch.cat(
             [t.transpose(1, 2).reshape(B, L, d) for t in (dq, dk, dv)],
             dim=-1)
-        return dqkv, None, None, None
+        return dqkv, None, None, None, None
 
 
-def flash_attention_packed(qkv, n_heads: int, mask=None, scale: float = 1.0):
+def flash_attention_packed(qkv, n_heads: int, mask=None, scale: float = 1.0,
+                           seg=None):
     """qkv: [B, L, 3*n_heads*64] bf16 (the fused projection output);
-    returns [B, L, n_heads*64] ready for the output projection."""
+    returns [B, L, n_heads*64] ready for the output projection.
+
+    mask: optional [B, L] f32 additive key bias; a bias <= -1e8 is treated
+    as fully masked (its probability is exactly 0 and wholly masked tiles
+    are skipped).  seg: optional [B, L] int32 segment ids of a packed batch,
+    exclusive with mask: position i attends to j iff seg[b, i] == seg[b, j].
+    Each seg row must be non-decreasing, with the padding tail carrying one
+    id above every real id; that is the caller's contract (check_segments
+    verifies it on the host), not checked on the device."""
+    _check_mask_seg(mask, seg)
     return _FlashAttentionPackedFn.apply(qkv.contiguous(), n_heads, mask,
-                                         scale)
+                                         scale, seg)
 
 
 def flash_supported(head_dim: int, L: int) -> bool:
@@ -444,6 +491,40 @@ def masked_mean_pool(x, mask=None):
     """pooled[b] = mean over valid rows of x[b]; x [B,L,D] bf16, mask [B,L]."""
     return _MaskedPoolFn.apply(x.contiguous(),
                                mask.contiguous() if mask is not None else None)
+
+
+class _SegmentPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, seg_start, seg_len, pos2seg):
+        if x.is_cuda:
+            pooled = hip_ops().segment_pool_fwd(x, seg_start, seg_len)
+        else:
+            pooled = reference.segment_pool_fwd(x, seg_start, seg_len,
+                                                pos2seg)
+        ctx.save_for_backward(seg_len, pos2seg)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dpooled):
+        seg_len, pos2seg = ctx.saved_tensors
+        dpooled = dpooled.contiguous()
+        if dpooled.is_cuda:
+            dx = hip_ops().segment_pool_bwd(dpooled, pos2seg, seg_len,
+                                            pos2seg.shape[0])
+        else:
+            dx = reference.segment_pool_bwd(dpooled, seg_len, pos2seg)
+        return dx, None, None, None
+
+
+def segment_mean_pool(x, seg_start, seg_len, pos2seg):
+    """Per-example mean-pool of a packed batch.
+
+    x: [T, D] — the [R, row_len, D] activations flattened over positions
+    (bf16 on the GPU, D % 8 == 0); seg_start/seg_len: [N] int32 first
+    position and length of every segment; pos2seg: [T] int32 segment of
+    every position, -1 at padding.  Returns pooled [N, D]; the gradient is
+    exactly zero at padding positions."""
+    return _SegmentPoolFn.apply(x.contiguous(), seg_start, seg_len, pos2seg)
 
 
 def adamw_step(p, grad, m, v, master, *, lr, beta1=0.9, beta2=0.999, eps=1e-8,

@@ -87,22 +87,59 @@ def softmax_bwd(dp: torch.Tensor, p: torch.Tensor, scale: float) -> torch.Tensor
     return (scale * pf * (dpf - dot)).to(p.dtype)
 
 
-def flash_attention_fwd(q, k, v, mask, scale):
-    """fp32 reference of the flash forward: returns (o in q.dtype, lse f32)."""
+def segment_bias(seg: torch.Tensor) -> torch.Tensor:
+    """Additive attention bias of a packed batch: seg [B, L] integer segment
+    ids -> [B, 1, L, L] f32, 0 where query and key share a segment and -1e9
+    (the padding mask's convention) where they do not."""
+    same = seg.unsqueeze(-1) == seg.unsqueeze(-2)
+    zero = torch.zeros((), dtype=torch.float32, device=seg.device)
+    return torch.where(same, zero, zero - 1e9).unsqueeze(1)
+
+
+def flash_attention_fwd(q, k, v, mask, scale, bias=None):
+    """fp32 reference of the flash forward: returns (o in q.dtype, lse f32).
+
+    mask: optional [B, L] additive key bias; bias: optional additive bias
+    broadcastable to [B, H, L, L] (segment_bias of a packed batch)."""
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if mask is not None:
         s = s + mask.float().view(mask.shape[0], 1, 1, -1)
+    if bias is not None:
+        s = s + bias
     lse = torch.logsumexp(s, dim=-1)
     p = torch.softmax(s, dim=-1)
     o = torch.matmul(p, v.float())
     return o.to(q.dtype), lse
 
 
-def p_from_lse(scores, mask, lse, scale):
+def p_from_lse(scores, mask, lse, scale, bias=None):
     s = scores.float() * scale
     if mask is not None:
         s = s + mask.float().view(mask.shape[0], 1, 1, -1)
+    if bias is not None:
+        s = s + bias
     return torch.exp(s - lse.unsqueeze(-1)).to(scores.dtype)
+
+
+def segment_pool_fwd(x, seg_start, seg_len, pos2seg):
+    """Per-segment mean over the flattened positions of a packed batch.
+
+    x [T, D]; seg_start/seg_len [N]; pos2seg [T] (segment of each position,
+    -1 for padding).  Returns pooled [N, D] in x.dtype (f32 accumulation)."""
+    n = seg_len.shape[0]
+    valid = pos2seg >= 0
+    acc = torch.zeros(n, x.shape[-1], dtype=torch.float32, device=x.device)
+    acc.index_add_(0, pos2seg[valid].long(), x[valid].float())
+    return (acc / seg_len.clamp(min=1).float().unsqueeze(-1)).to(x.dtype)
+
+
+def segment_pool_bwd(dpooled, seg_len, pos2seg):
+    """dx[t] = dpooled[pos2seg[t]] / seg_len; exact zeros at padding."""
+    valid = pos2seg >= 0
+    idx = pos2seg.clamp(min=0).long()
+    g = dpooled.float() / seg_len.clamp(min=1).float().unsqueeze(-1)
+    dx = g[idx] * valid.unsqueeze(-1).float()
+    return dx.to(dpooled.dtype)
 
 
 def adamw_step(

@@ -38,7 +38,9 @@ class ClassifierService:
     def __init__(self, ckpt_dir: Optional[str] = None,
                  model: str = "mltc-base", seq: int = 256,
                  threshold: float = 0.5, device: Optional[str] = None,
-                 repo_prefix: bool = False):
+                 repo_prefix: bool = False, pack: bool = False):
+        # pack: run one request's texts as a packed batch (data.packing)
+        self.pack = pack
         self.seq = seq
         self.threshold = threshold
         self.repo_prefix = repo_prefix
@@ -77,9 +79,16 @@ class ClassifierService:
         inputs = texts
         if self.repo_prefix:
             inputs = [f"REPO_{r} {t}" for r, t in zip(repos, texts)]
-        toks, mask = self.tok.encode_batch(inputs, self.seq,
-                                           device=self.device)
-        logits = self.trainer.model(toks, mask)
+        if self.pack and inputs:
+            pb = self.tok.encode_packed(inputs, self.seq,
+                                        (self.seq + 63) // 64 * 64,
+                                        device=self.device)
+            logits = {h: pb.unpermute(v) for h, v in
+                      self.trainer.model(pb.tokens, packing=pb).items()}
+        else:
+            toks, mask = self.tok.encode_batch(inputs, self.seq,
+                                               device=self.device)
+            logits = self.trainer.model(toks, mask)
         sp = torch.sigmoid(logits["strategy"].float()) > self.threshold
         pp = torch.sigmoid(logits["property"].float()) > self.threshold
         stg = logits["stage"].float().argmax(-1)

@@ -22,6 +22,7 @@ import torch
 import torch.distributed as dist
 
 from tosem2021_amd import ops
+from tosem2021_amd.data.packing import PackedBatch
 from tosem2021_amd.models import MLTCConfig, build_model
 from tosem2021_amd.parallel.ddp import BucketedAllReduce
 from tosem2021_amd.utils.metrics import get_metrics
@@ -108,11 +109,20 @@ class Trainer:
         t = (s - c.warmup_steps) / max(c.total_steps - c.warmup_steps, 1)
         return c.lr * 0.5 * (1.0 + math.cos(math.pi * min(t, 1.0)))
 
+    def _forward(self, tokens, attn_mask):
+        """tokens is a [B, L] tensor (with its optional attn_mask) or a
+        data.packing.PackedBatch (attn_mask None; logits in segment order)."""
+        if isinstance(tokens, PackedBatch):
+            return self.model(tokens.tokens, attn_mask, packing=tokens)
+        return self.model(tokens, attn_mask)
+
     # ---- one optimization step ----------------------------------------------
     def step_accum(self, micro_batches) -> float:
         """One optimizer step over several micro-batches (gradient
         accumulation): collectives fire only on the last micro-backward,
-        and the 1/n_micro mean folds into the AdamW grad scale."""
+        and the 1/n_micro mean folds into the AdamW grad scale.  A
+        micro-batch is (tokens, attn_mask, labels) or, packed,
+        (PackedBatch, None, labels in segment order)."""
         micro_batches = list(micro_batches)
         n = len(micro_batches)
         with trace("train_step_accum", step=self.step_num + 1, micro=n):
@@ -120,7 +130,7 @@ class Trainer:
             total_loss = 0.0
             for i, (tokens, attn_mask, labels) in enumerate(micro_batches):
                 self.ddp.sync = (i == n - 1)
-                logits = self.model(tokens, attn_mask)
+                logits = self._forward(tokens, attn_mask)
                 loss = self.model.loss(logits, labels)
                 loss.backward()
                 total_loss += float(loss.detach())
@@ -137,11 +147,13 @@ class Trainer:
         get_metrics().observe_step(self.step_num, loss=total_loss / n, lr=lr)
         return total_loss / n
 
-    def step(self, tokens: torch.Tensor, attn_mask: Optional[torch.Tensor],
+    def step(self, tokens, attn_mask: Optional[torch.Tensor],
              labels: Dict[str, torch.Tensor]) -> float:
+        """tokens: [B, L] tensor, or a PackedBatch with attn_mask None and
+        the labels in segment order (TaxonomyDataset.packed_batches)."""
         with trace("train_step", step=self.step_num + 1):
             self.flat.zero_grad()
-            logits = self.model(tokens, attn_mask)
+            logits = self._forward(tokens, attn_mask)
             loss = self.model.loss(logits, labels)
             loss.backward()
             self.ddp.finalize()
