@@ -72,20 +72,41 @@ bias_gelu_fwd_kernel(const short* __restrict__ x, const short* __restrict__ b,
   }
 }
 
+}  // extern "C" (the template below needs C++ linkage)
+
 // dbias: each thread's per-packet fixed 8-column windows accumulate in
-// registers; 32 LDS atomics per thread at the END (not per element), then
-// one per-block f32 partial row for the deterministic colsum reduction.
+// registers and merge once at the END (not per element) into one per-block
+// f32 partial row for the deterministic colsum reduction.
+//
+// OWNED (D % BG_TILE == 0, i.e. D a multiple of 2048): a column is only
+// ever touched by ONE thread of the block, whose packets add to it in
+// program order, so the LDS row needs no ordering between threads.
+//
+// !OWNED, fast path (any other D whose grid stride is a multiple of D):
+// threads of different waves share columns (t and t+128 at D=1024), so the
+// merge goes through a [BG_PK * BG_TILE] LDS slab instead: every thread
+// stores its 32 partials at the block-relative element index they belong
+// to, and the thread that owns column c adds the slab entries e0, e0 + D,
+// e0 + 2D, ... in ascending order.  Same order on every run, no atomics.
+//
+// The generic fallback (grid stride not a multiple of D: D >= 16392 with an
+// odd factor) still merges per element with LDS atomics.
+template <bool OWNED>
 __global__ void __launch_bounds__(BG_BLOCK)
 bias_gelu_bwd_kernel(const short* __restrict__ dy, const short* __restrict__ x,
                      const short* __restrict__ b, short* __restrict__ dx,
                      float* __restrict__ ws_dbias, long n_elem, int D) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sdb = (float*)smem;  // [D]
-  for (int i = threadIdx.x; i < D; i += BG_BLOCK) sdb[i] = 0.f;
-  __syncthreads();
+  // OWNED and the fallback: [D] block partial; !OWNED fast path: the slab
+  float* sdb = (float*)smem;
   long tile0 = (long)blockIdx.x * (BG_TILE * BG_PK) + threadIdx.x * 8;
   long stride = (long)gridDim.x * (BG_TILE * BG_PK);
-  if (stride % D == 0) {
+  const bool fast = stride % D == 0;
+  if (OWNED || !fast) {
+    for (int i = threadIdx.x; i < D; i += BG_BLOCK) sdb[i] = 0.f;
+    __syncthreads();
+  }
+  if (fast) {
     float acc[BG_PK * 8] = {0.f};
     int cols[BG_PK];
     float bb[BG_PK * 8];
@@ -120,10 +141,30 @@ bias_gelu_bwd_kernel(const short* __restrict__ dy, const short* __restrict__ x,
         *(short8_t*)(dx + i + p * BG_TILE) = o;
       }
     }
+    if (OWNED) {
 #pragma unroll
-    for (int p = 0; p < BG_PK; ++p)
+      for (int p = 0; p < BG_PK; ++p)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) atomicAdd(&sdb[cols[p] + j], acc[8 * p + j]);
+        for (int j = 0; j < 8; ++j)
+          atomicAdd(&sdb[cols[p] + j], acc[8 * p + j]);
+    } else {
+#pragma unroll
+      for (int p = 0; p < BG_PK; ++p)
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          sdb[p * BG_TILE + threadIdx.x * 8 + j] = acc[8 * p + j];
+      __syncthreads();
+      // slab entry e holds the partial of column (off + e) % D
+      const int off = (int)((long)blockIdx.x * (BG_TILE * BG_PK) % D);
+      float* out = ws_dbias + (long)blockIdx.x * D;
+      for (int c = threadIdx.x; c < D; c += BG_BLOCK) {
+        float s = 0.f;
+        for (int e = (c - off + D) % D; e < BG_TILE * BG_PK; e += D)
+          s += sdb[e];
+        out[c] = s;
+      }
+      return;
+    }
   } else {
     long idx0 = ((long)blockIdx.x * BG_BLOCK + threadIdx.x) * 8;
     long gstride = (long)gridDim.x * BG_BLOCK * 8;
@@ -149,6 +190,8 @@ bias_gelu_bwd_kernel(const short* __restrict__ dy, const short* __restrict__ x,
   for (int i = threadIdx.x; i < D; i += BG_BLOCK) out[i] = sdb[i];
 }
 
+extern "C" {
+
 hipError_t bias_gelu_fwd_launch(const void* x, const void* b, void* y,
                                 long n_elem, int D, int grid, hipStream_t s) {
   bias_gelu_fwd_kernel<<<grid, BG_BLOCK, 0, s>>>((const short*)x, (const short*)b,
@@ -159,10 +202,20 @@ hipError_t bias_gelu_fwd_launch(const void* x, const void* b, void* y,
 hipError_t bias_gelu_bwd_launch(const void* dy, const void* x, const void* b,
                                 void* dx, void* ws_dbias, long n_elem, int D,
                                 int grid, hipStream_t s) {
+  // [D] block partial, or the [BG_PK * BG_TILE] merge slab of the !OWNED
+  // fast path, whichever the kernel will use
   size_t shm = (size_t)D * sizeof(float);
-  bias_gelu_bwd_kernel<<<grid, BG_BLOCK, shm, s>>>(
-      (const short*)dy, (const short*)x, (const short*)b, (short*)dx,
-      (float*)ws_dbias, n_elem, D);
+  if (D % BG_TILE == 0) {
+    bias_gelu_bwd_kernel<true><<<grid, BG_BLOCK, shm, s>>>(
+        (const short*)dy, (const short*)x, (const short*)b, (short*)dx,
+        (float*)ws_dbias, n_elem, D);
+  } else {
+    if ((long)grid * (BG_TILE * BG_PK) % D == 0)
+      shm = (size_t)BG_TILE * BG_PK * sizeof(float);
+    bias_gelu_bwd_kernel<false><<<grid, BG_BLOCK, shm, s>>>(
+        (const short*)dy, (const short*)x, (const short*)b, (short*)dx,
+        (float*)ws_dbias, n_elem, D);
+  }
   return hipGetLastError();
 }
 

@@ -471,39 +471,29 @@ ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
   }
 }
 
-extern "C" {
-
-// dx = rstd * (dyg - mean(dyg) - xhat * mean(dyg * xhat)),  dyg = dy * gamma
-// Per-block dgamma/dbeta partials go to ws_dgamma/ws_dbeta [gridDim.x, D]
-// (deterministic two-stage column reduction, no atomics).
+// General-width backward, any D % 8 == 0 up to MAXP * 512 (the widths
+// without an ln_bwd_t2 instance: 128, 256, 2048, 4096, odd ones like 136).
+//   dx = rstd * (dyg - mean(dyg) - xhat * mean(dyg * xhat)),  dyg = dy * gamma
+// One wave per row; lane l owns columns (p * 64 + l) * 8 + j for its whole
+// row loop, so the row and the dgamma/dbeta partials stay in registers.
+// The four waves of a block then merge their partials through LDS one wave
+// at a time, wave 0 first: every column is summed in the same order on
+// every run, with no atomics.  One ws row per block.
+template <int MAXP>
 __global__ void __launch_bounds__(BLOCK)
-ln_bwd_kernel(const short* __restrict__ dy, const short* __restrict__ x,
-              const short* __restrict__ gamma, const float* __restrict__ mean_in,
-              const float* __restrict__ rstd_in,
-              const short* __restrict__ ds_extra,  // optional += into dx
-              short* __restrict__ dx,
-              float* __restrict__ ws_dgamma, float* __restrict__ ws_dbeta,
-              int N, int D) {
+ln_bwd_g(const short* __restrict__ dy, const short* __restrict__ x,
+         const short* __restrict__ gamma, const float* __restrict__ mean_in,
+         const float* __restrict__ rstd_in,
+         const short* __restrict__ ds_extra,  // optional += into dx
+         short* __restrict__ dx,
+         float* __restrict__ ws_dgamma, float* __restrict__ ws_dbeta,
+         int N, int D) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sg = (float*)smem;          // [D] dgamma partial for this block
   float* sb = sg + D;                // [D] dbeta partial
-  for (int i = threadIdx.x; i < D; i += BLOCK) { sg[i] = 0.f; sb[i] = 0.f; }
-  __syncthreads();
-
-  const int pkts = D / (WAVE * 8);
-  // bwd register-cached path capped at 2 packets (D <= 1024, the flagship
-  // width); wider D takes the re-read path. 4 packets put the kernel at 256
-  // VGPR = 1-2 waves/SIMD.
-  // Each (wave,lane,j) owns a FIXED column set across its whole row loop, so
-  // dgamma/dbeta partials accumulate in registers and hit the LDS once per
-  // wave at the end (the per-element LDS atomics were 8.5 ms/step in the
-  // baseline profile — profiles/r01_kernel_stats_baseline.md).
-#define MAX_PKT_BWD 2
-  float dg_acc[MAX_PKT_BWD * 8] = {0.f};
-  float db_acc[MAX_PKT_BWD * 8] = {0.f};
-  const bool cached = pkts <= MAX_PKT_BWD && D == pkts * WAVE * 8;
+  float dg_acc[MAXP * 8] = {0.f}, db_acc[MAXP * 8] = {0.f};
   for (int row = blockIdx.x * WAVES_PER_BLOCK + wid; row < N;
        row += gridDim.x * WAVES_PER_BLOCK) {
     const short* dyr = dy + (long)row * D;
@@ -511,103 +501,135 @@ ln_bwd_kernel(const short* __restrict__ dy, const short* __restrict__ x,
     const short* der = ds_extra ? ds_extra + (long)row * D : nullptr;
     short* dxr = dx + (long)row * D;
     const float mean = mean_in[row], rstd = rstd_in[row];
-    if (pkts <= MAX_PKT_BWD && D == pkts * WAVE * 8) {
-      // two register arrays only (xh, dyg); dgamma/dbeta accumulate in the
-      // first pass (the third array pushed the kernel to 256 VGPR = 1
-      // wave/SIMD)
-      float xh[MAX_PKT_BWD * 8], dyg[MAX_PKT_BWD * 8];
-      float s1 = 0.f, s2 = 0.f;
+    short8_t vd[MAXP], vx[MAXP], vg[MAXP];
+    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-      for (int p = 0; p < MAX_PKT_BWD; ++p) {
-        if (p >= pkts) break;
-        int base = (p * WAVE + lane) * 8;
-        short8_t vd = *(const short8_t*)(dyr + base);
-        short8_t vx = *(const short8_t*)(xr + base);
-        short8_t g8 = *(const short8_t*)(gamma + base);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int k = p * 8 + j;
-          float d = bf16_to_f32(vd[j]);
-          float h = (bf16_to_f32(vx[j]) - mean) * rstd;
-          float g = d * bf16_to_f32(g8[j]);
-          xh[k] = h; dyg[k] = g;
-          dg_acc[k] += d * h;
-          db_acc[k] += d;
-          s1 += g; s2 += g * h;
-        }
-      }
-      s1 = wave_sum(s1) / (float)D;
-      s2 = wave_sum(s2) / (float)D;
-#pragma unroll
-      for (int p = 0; p < MAX_PKT_BWD; ++p) {
-        if (p >= pkts) break;
-        int base = (p * WAVE + lane) * 8;
-        short8_t ev;
-        if (der) ev = *(const short8_t*)(der + base);
-        short8_t o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int k = p * 8 + j;
-          float d_ = rstd * (dyg[k] - s1 - xh[k] * s2);
-          if (der) d_ += bf16_to_f32(ev[j]);
-          o[j] = f32_to_bf16(d_);
-        }
-        *(short8_t*)(dxr + base) = o;
-      }
-    } else {
-      float s1 = 0.f, s2 = 0.f;
-      for (int i = lane * 8; i < D; i += WAVE * 8) {
-        short8_t vd = *(const short8_t*)(dyr + i);
-        short8_t vx = *(const short8_t*)(xr + i);
-        short8_t g8 = *(const short8_t*)(gamma + i);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float g = bf16_to_f32(vd[j]) * bf16_to_f32(g8[j]);
-          float h = (bf16_to_f32(vx[j]) - mean) * rstd;
-          s1 += g; s2 += g * h;
-        }
-      }
-      s1 = wave_sum(s1) / (float)D;
-      s2 = wave_sum(s2) / (float)D;
-      for (int i = lane * 8; i < D; i += WAVE * 8) {
-        short8_t vd = *(const short8_t*)(dyr + i);
-        short8_t vx = *(const short8_t*)(xr + i);
-        short8_t g8 = *(const short8_t*)(gamma + i);
-        short8_t ev;
-        if (der) ev = *(const short8_t*)(der + i);
-        short8_t o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float d = bf16_to_f32(vd[j]);
-          float h = (bf16_to_f32(vx[j]) - mean) * rstd;
-          float g = d * bf16_to_f32(g8[j]);
-          float d_ = rstd * (g - s1 - h * s2);
-          if (der) d_ += bf16_to_f32(ev[j]);
-          o[j] = f32_to_bf16(d_);
-          atomicAdd(&sg[i + j], d * h);
-          atomicAdd(&sb[i + j], d);
-        }
-        *(short8_t*)(dxr + i) = o;
-      }
-    }
-  }
-  if (cached) {
-#pragma unroll
-    for (int p = 0; p < MAX_PKT_BWD; ++p) {
-      if (p >= pkts) break;
+    for (int p = 0; p < MAXP; ++p) {
       int base = (p * WAVE + lane) * 8;
+      if (base >= D) continue;
+      vd[p] = *(const short8_t*)(dyr + base);
+      vx[p] = *(const short8_t*)(xr + base);
+      vg[p] = *(const short8_t*)(gamma + base);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        atomicAdd(&sg[base + j], dg_acc[p * 8 + j]);
-        atomicAdd(&sb[base + j], db_acc[p * 8 + j]);
+        float d = bf16_to_f32(vd[p][j]);
+        float h = (bf16_to_f32(vx[p][j]) - mean) * rstd;
+        float g = d * bf16_to_f32(vg[p][j]);
+        dg_acc[p * 8 + j] += d * h;
+        db_acc[p * 8 + j] += d;
+        s1 += g; s2 += g * h;
       }
     }
+    s1 = wave_sum(s1) / (float)D;
+    s2 = wave_sum(s2) / (float)D;
+#pragma unroll
+    for (int p = 0; p < MAXP; ++p) {
+      int base = (p * WAVE + lane) * 8;
+      if (base >= D) continue;
+      short8_t ev;
+      if (der) ev = *(const short8_t*)(der + base);
+      short8_t o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float h = (bf16_to_f32(vx[p][j]) - mean) * rstd;
+        float g = bf16_to_f32(vd[p][j]) * bf16_to_f32(vg[p][j]);
+        float d_ = rstd * (g - s1 - h * s2);
+        if (der) d_ += bf16_to_f32(ev[j]);
+        o[j] = f32_to_bf16(d_);
+      }
+      *(short8_t*)(dxr + base) = o;
+    }
   }
-  __syncthreads();
+  // fixed-order merge: wave w adds its partials after waves 0..w-1 have
+  // (a wave without rows adds zeros); all four barriers are block-uniform
+  for (int w = 0; w < WAVES_PER_BLOCK; ++w) {
+    if (wid == w) {
+#pragma unroll
+      for (int p = 0; p < MAXP; ++p) {
+        int base = (p * WAVE + lane) * 8;
+        if (base >= D) continue;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float pg = w ? sg[base + j] : 0.f, pb = w ? sb[base + j] : 0.f;
+          sg[base + j] = pg + dg_acc[p * 8 + j];
+          sb[base + j] = pb + db_acc[p * 8 + j];
+        }
+      }
+    }
+    __syncthreads();
+  }
   float* og = ws_dgamma + (long)blockIdx.x * D;
   float* ob = ws_dbeta + (long)blockIdx.x * D;
   for (int i = threadIdx.x; i < D; i += BLOCK) { og[i] = sg[i]; ob[i] = sb[i]; }
 }
+
+// Widths above LN_BWD_G_MAX_D: the partials no longer fit in registers, so
+// every wave accumulates into its OWN ws row in global memory (the lane that
+// owns a column is the only one that ever touches it: plain read-add-write,
+// no atomics), and the colsum reduces the gridDim.x * WAVES_PER_BLOCK rows in
+// fixed order like the template path's.
+#define LN_BWD_G_MAX_D 4096
+__global__ void __launch_bounds__(BLOCK)
+ln_bwd_wide_kernel(const short* __restrict__ dy, const short* __restrict__ x,
+                   const short* __restrict__ gamma,
+                   const float* __restrict__ mean_in,
+                   const float* __restrict__ rstd_in,
+                   const short* __restrict__ ds_extra,
+                   short* __restrict__ dx, float* __restrict__ ws_dgamma,
+                   float* __restrict__ ws_dbeta, int N, int D) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+  float* og = ws_dgamma + (long)(blockIdx.x * WAVES_PER_BLOCK + wid) * D;
+  float* ob = ws_dbeta + (long)(blockIdx.x * WAVES_PER_BLOCK + wid) * D;
+  for (int i = lane * 8; i < D; i += WAVE * 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { og[i + j] = 0.f; ob[i + j] = 0.f; }
+  }
+  for (int row = blockIdx.x * WAVES_PER_BLOCK + wid; row < N;
+       row += gridDim.x * WAVES_PER_BLOCK) {
+    const short* dyr = dy + (long)row * D;
+    const short* xr = x + (long)row * D;
+    const short* der = ds_extra ? ds_extra + (long)row * D : nullptr;
+    short* dxr = dx + (long)row * D;
+    const float mean = mean_in[row], rstd = rstd_in[row];
+    float s1 = 0.f, s2 = 0.f;
+    for (int i = lane * 8; i < D; i += WAVE * 8) {
+      short8_t vd = *(const short8_t*)(dyr + i);
+      short8_t vx = *(const short8_t*)(xr + i);
+      short8_t g8 = *(const short8_t*)(gamma + i);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float g = bf16_to_f32(vd[j]) * bf16_to_f32(g8[j]);
+        float h = (bf16_to_f32(vx[j]) - mean) * rstd;
+        s1 += g; s2 += g * h;
+      }
+    }
+    s1 = wave_sum(s1) / (float)D;
+    s2 = wave_sum(s2) / (float)D;
+    for (int i = lane * 8; i < D; i += WAVE * 8) {
+      short8_t vd = *(const short8_t*)(dyr + i);
+      short8_t vx = *(const short8_t*)(xr + i);
+      short8_t g8 = *(const short8_t*)(gamma + i);
+      short8_t ev;
+      if (der) ev = *(const short8_t*)(der + i);
+      short8_t o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float d = bf16_to_f32(vd[j]);
+        float h = (bf16_to_f32(vx[j]) - mean) * rstd;
+        float g = d * bf16_to_f32(g8[j]);
+        float d_ = rstd * (g - s1 - h * s2);
+        if (der) d_ += bf16_to_f32(ev[j]);
+        o[j] = f32_to_bf16(d_);
+        og[i + j] += d * h;
+        ob[i + j] += d;
+      }
+      *(short8_t*)(dxr + i) = o;
+    }
+  }
+}
+
+extern "C" {
 
 // Column-sum of the [R, D] f32 partials workspace into [D] f32.
 // Two-stage split-row reduction: the single-threaded-column version ran 4
@@ -768,15 +790,32 @@ hipError_t ln_bwd_launch(const void* dy, const void* x, const void* gamma,
           (const float*)mean, (const float*)rstd, nullptr, (short*)dx,        \
           (float*)ws_dgamma, (float*)ws_dbeta, N, D);                         \
   } while (0)
+#define LNB_G(P)                                                              \
+  ln_bwd_g<P><<<grid, BLOCK, shm, stream>>>(                                  \
+      (const short*)dy, (const short*)x, (const short*)gamma,                 \
+      (const float*)mean, (const float*)rstd, (const short*)ds_extra,         \
+      (short*)dx, (float*)ws_dgamma, (float*)ws_dbeta, N, D)
   if (D == 512) LNB_T(1);
   else if (D == 1024) LNB_T(2);
+  else if (D <= 512) LNB_G(1);
+  else if (D <= 1024) LNB_G(2);
+  else if (D <= 2048) LNB_G(4);
+  else if (D <= LN_BWD_G_MAX_D) LNB_G(8);
   else
-    ln_bwd_kernel<<<grid, BLOCK, shm, stream>>>(
+    ln_bwd_wide_kernel<<<grid, BLOCK, 0, stream>>>(
         (const short*)dy, (const short*)x, (const short*)gamma,
         (const float*)mean, (const float*)rstd, (const short*)ds_extra,
         (short*)dx, (float*)ws_dgamma, (float*)ws_dbeta, N, D);
+#undef LNB_G
 #undef LNB_T
   return hipGetLastError();
+}
+
+// Workspace rows ln_bwd_launch writes for a grid of `grid` blocks: one per
+// wave on the template and wide paths, one per block on the general path.
+int ln_bwd_ws_rows(int D, int grid) {
+  const bool per_wave = D == 512 || D == 1024 || D > LN_BWD_G_MAX_D;
+  return per_wave ? grid * WAVES_PER_BLOCK : grid;
 }
 
 // Adaptive split count (round 2): the fixed 64-way split left a D=1024

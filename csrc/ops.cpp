@@ -17,6 +17,7 @@ hipError_t ln_fwd_launch(const void*, const void*, const void*, const void*,
 hipError_t ln_bwd_launch(const void*, const void*, const void*, const void*,
                          const void*, const void*, void*, void*, void*, int,
                          int, int, hipStream_t);
+int ln_bwd_ws_rows(int, int);
 hipError_t colsum_launch(const void*, void*, void*, int, int, hipStream_t);
 hipError_t bias_gelu_fwd_launch(const void*, const void*, void*, long, int,
                                 int, hipStream_t);
@@ -241,14 +242,15 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
   check_bf16(dy, "dy"); check_bf16(x, "x"); check_bf16(gamma, "gamma");
   const int D = (int)x.size(-1);
   const long N = x.numel() / D;
+  TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8, got ", D);
   auto dx = torch::empty_like(x);
   // bwd grid stays modest: the [rows, D] dgamma/dbeta workspace and its
   // column-sum scale linearly with the grid
-  int grid = (int)std::min<long>((N + 3) / 4, 1024);
-  // the template path (D in {512, 1024}) writes ONE ws row per wave
-  // (deterministic, no atomics); the general path writes one per block
-  const bool templ = (D == 512 || D == 1024);
-  long ws_rows = templ ? (long)grid * 4 : (long)grid;
+  // (D > 4096 keeps one row per WAVE in global memory: a quarter of the grid)
+  int grid = (int)std::min<long>((N + 3) / 4, D > 4096 ? 256 : 1024);
+  // one ws row per wave or per block, depending on the kernel the launcher
+  // picks for this D; either way the rows are reduced in fixed order
+  long ws_rows = ln_bwd_ws_rows(D, grid);
   auto opts = x.options().dtype(torch::kFloat32);
   auto ws_dg = torch::empty({ws_rows, D}, opts);
   auto ws_db = torch::empty({ws_rows, D}, opts);
@@ -293,6 +295,7 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
   check_bf16(dy, "dy"); check_bf16(x, "x"); check_bf16(b, "b");
   const int D = (int)x.size(-1);
   const long n = x.numel();
+  TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8");
   auto dx = torch::empty_like(x);
   int grid = (int)std::min<long>((n / 32 + 255) / 256, 1024);
   // round the grid up to a multiple of D/gcd(D, 256*32) so the kernel's

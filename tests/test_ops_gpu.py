@@ -92,7 +92,10 @@ def test_softmax(B, H, Lq, Lk):
     dpg = _bf16(torch.randn(B, H, Lq, Lk))
     ds = ops.hip_ops().softmax_bwd(dpg, p, scale)
     dse = ref.softmax_bwd(dpg.float().cpu(), p.float().cpu(), scale)
-    assert torch.allclose(ds.float().cpu(), dse, atol=8e-3, rtol=2e-2)
+    # |ds| peaks near 4e-3, below the atol: allclose alone passes an all-zero
+    # ds, the helper's relative bound (4 x the bf16 rounding floor) does not
+    from test_ops_gpu_scale import assert_close
+    assert_close(ds.cpu(), dse, "ds", atol=8e-3, rtol=2e-2)
 
 
 def test_softmax_no_mask():
