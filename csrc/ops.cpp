@@ -30,6 +30,12 @@ hipError_t softmax_bwd_launch(const void*, const void*, void*, long, int,
 hipError_t adamw_launch(void*, const void*, int, void*, void*, void*, long,
                         float, float, float, float, float, int, float, int,
                         hipStream_t);
+hipError_t adamw_clipped_launch(void*, const void*, int, void*, void*, void*,
+                                long, float, float, float, float, float, int,
+                                const void*, int, hipStream_t);
+int grad_norm_grid(long);
+hipError_t grad_clip_state_launch(const void*, int, long, float, float, void*,
+                                  void*, hipStream_t);
 hipError_t qkv_repack_launch(const void*, void*, int, int, int, int, int,
                              hipStream_t);
 hipError_t out_repack_launch(const void*, void*, int, int, int, int, int,
@@ -368,6 +374,58 @@ void adamw_step(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
                          v.data_ptr(), master.data_ptr(), n, (float)lr,
                          (float)beta1, (float)beta2, (float)eps, (float)wd,
                          (int)step, (float)grad_scale, grid, cur_stream()));
+}
+
+// The flat gradient buffer of the clipped step: bf16 or f32, contiguous, a
+// multiple of 8 elements and 16-byte aligned (16 B per lane loads).
+int check_flat_grad(const torch::Tensor& grad) {
+  TORCH_CHECK(grad.is_contiguous() && grad.device().is_cuda(), "bad grad");
+  int gf32 = grad.scalar_type() == torch::kFloat32;
+  TORCH_CHECK(gf32 || grad.scalar_type() == torch::kBFloat16,
+              "grad must be f32 or bf16");
+  TORCH_CHECK(grad.numel() > 0 && grad.numel() % 8 == 0,
+              "flat gradient buffer must be padded to 8 elems");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(grad.data_ptr()) % 16 == 0,
+              "flat gradient buffer must be 16-byte aligned");
+  return gf32;
+}
+
+// clip_state = {norm, scale, finite, sumsq} on the device (csrc/grad_norm.hip);
+// nothing is read back here.
+torch::Tensor grad_clip_state(torch::Tensor grad, double grad_scale,
+                              double max_norm) {
+  int gf32 = check_flat_grad(grad);
+  TORCH_CHECK(max_norm > 0, "max_norm must be greater than 0");
+  const long n = grad.numel();
+  auto opts = torch::TensorOptions().dtype(torch::kFloat32)
+                  .device(grad.device());
+  auto partials = torch::empty({grad_norm_grid(n)}, opts);
+  auto state = torch::empty({4}, opts);
+  CHECK_HIP(grad_clip_state_launch(grad.data_ptr(), gf32, n,
+                                   (float)grad_scale, (float)max_norm,
+                                   partials.data_ptr(), state.data_ptr(),
+                                   cur_stream()));
+  return state;
+}
+
+void adamw_step_clipped(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
+                        torch::Tensor v, torch::Tensor master, double lr,
+                        double beta1, double beta2, double eps, double wd,
+                        long step, torch::Tensor clip_state) {
+  check_bf16(p, "p"); check_f32(m, "m"); check_f32(v, "v");
+  check_f32(master, "master"); check_f32(clip_state, "clip_state");
+  int gf32 = check_flat_grad(grad);
+  TORCH_CHECK(clip_state.numel() == 4, "clip_state must hold 4 floats");
+  const long n = p.numel();
+  TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n &&
+              master.numel() == n, "size mismatch");
+  int grid = (int)std::min<long>((n / 4 + 255) / 256, 2048);
+  CHECK_HIP(adamw_clipped_launch(p.data_ptr(), grad.data_ptr(), gf32,
+                                 m.data_ptr(), v.data_ptr(),
+                                 master.data_ptr(), n, (float)lr,
+                                 (float)beta1, (float)beta2, (float)eps,
+                                 (float)wd, (int)step, clip_state.data_ptr(),
+                                 grid, cur_stream()));
 }
 
 torch::Tensor qkv_repack(torch::Tensor qkv, long H, bool backward) {
@@ -767,4 +825,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_fwd", &softmax_fwd, "fused scaled masked softmax fwd");
   m.def("softmax_bwd", &softmax_bwd, "fused softmax bwd");
   m.def("adamw_step", &adamw_step, "fused AdamW over flat params");
+  m.def("grad_clip_state", &grad_clip_state,
+        "deterministic global grad norm -> device {norm, scale, finite, "
+        "sumsq}");
+  m.def("adamw_step_clipped", &adamw_step_clipped,
+        "fused AdamW reading its grad scale / skip flag from clip_state");
 }

@@ -29,6 +29,7 @@ ext = CUDAExtension(
         "csrc/bias_gelu.hip",
         "csrc/softmax.hip",
         "csrc/adamw.hip",
+        "csrc/grad_norm.hip",
         "csrc/repack.hip",
         "csrc/flash_attn.hip",
         "csrc/wgrad_gemm.hip",

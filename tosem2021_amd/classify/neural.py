@@ -209,8 +209,13 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                      dump_probs_path: Optional[str] = None,
                      augment: float = 0.0,
                      split_seed: Optional[int] = None,
-                     pack: bool = False) -> dict:
+                     pack: bool = False,
+                     max_grad_norm: float = 0.0) -> dict:
     """Fine-tune MLTC on `taxonomy_path`'s labeled rows.
+
+    `max_grad_norm` > 0 clips the global gradient norm and skips steps whose
+    gradient is not finite (TrainConfig.max_grad_norm); the result then also
+    reports `skipped_steps` and `last_grad_norm`.
 
     `pack` trains and evaluates on packed batches (data.packing): each
     step's `batch` examples share rows of `seq` tokens instead of one padded
@@ -237,7 +242,8 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
     tok = CodeTokenizer(cfg.vocab_size)
     tcfg = TrainConfig(model=model, lr=lr, warmup_steps=min(50, steps // 10),
                        total_steps=steps, ckpt_dir=ckpt_dir,
-                       dtype="bf16" if dev.type == "cuda" else "f32")
+                       dtype="bf16" if dev.type == "cuda" else "f32",
+                       max_grad_norm=max_grad_norm)
     trainer = Trainer(tcfg, device=dev, model_cfg=cfg)
     trainer.model.set_pos_weights(
         {k: v.to(dev) for k, v in train_ds.pos_weights().items()})
@@ -255,7 +261,7 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
         pre_cfg = TrainConfig(model=model, lr=lr,
                               warmup_steps=min(50, pretrain_steps // 10),
                               total_steps=pretrain_steps,
-                              dtype=tcfg.dtype)
+                              dtype=tcfg.dtype, max_grad_norm=max_grad_norm)
         pre_tr = Trainer(pre_cfg, device=dev, model_cfg=cfg)
         pre_tr.model.set_pos_weights(
             {k: v.to(dev) for k, v in pre_ds.pos_weights().items()})
@@ -289,7 +295,12 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                     "seed": seed}, dump_probs_path)
     if ckpt_dir:
         trainer.save()
+    clip = {}
+    if max_grad_norm > 0:
+        clip = {"skipped_steps": trainer.skipped_steps,
+                "last_grad_norm": trainer.metrics.get("grad_norm")}
     return {
+        **clip,
         "steps": trainer.step_num,
         "epochs": epoch,
         "train_time_s": round(train_time, 2),

@@ -142,7 +142,8 @@ def cmd_train(args):
         focal_gamma_property=args.focal_gamma_property,
         label_smoothing=args.label_smoothing, eval_every=args.eval_every,
         seed=args.seed, dump_probs_path=args.dump_probs,
-        augment=args.augment, split_seed=args.split_seed, pack=args.pack)
+        augment=args.augment, split_seed=args.split_seed, pack=args.pack,
+        max_grad_norm=args.clip_grad_norm)
     print(json.dumps(res, indent=2))
 
 
@@ -246,6 +247,9 @@ def main(argv=None):
     p.add_argument("--pack", action="store_true",
                    help="train and evaluate on packed batches (several "
                         "examples per row, segment-aware attention)")
+    p.add_argument("--clip-grad-norm", type=float, default=0.0,
+                   help="clip the global gradient norm to this value and "
+                        "skip steps with a non-finite gradient (0 = off)")
     p.set_defaults(fn=cmd_train)
 
     args = ap.parse_args(argv)

@@ -536,3 +536,29 @@ def adamw_step(p, grad, m, v, master, *, lr, beta1=0.9, beta2=0.999, eps=1e-8,
     else:
         reference.adamw_step(p, grad, m, v, master, lr, beta1, beta2, eps, wd,
                              step, grad_scale)
+
+
+def grad_clip_state(grad, *, grad_scale=1.0, max_norm):
+    """Global-norm clip state of the flat gradient buffer, on grad's device:
+    f32[4] = {norm, scale, finite, sumsq} with norm = grad_scale * |grad|,
+    scale = grad_scale * min(1, max_norm / (norm + 1e-6)) and finite = 0 for
+    an inf/NaN gradient (csrc/grad_norm.hip).  Deterministic; no host sync.
+    max_norm=inf measures and guards without clipping."""
+    if not max_norm > 0:
+        raise ValueError(f"max_norm must be greater than 0, got {max_norm}")
+    if grad.is_cuda:
+        return hip_ops().grad_clip_state(grad, grad_scale, max_norm)
+    return reference.grad_clip_state(grad, grad_scale, max_norm)
+
+
+def adamw_step_clipped(p, grad, m, v, master, *, lr, beta1=0.9, beta2=0.999,
+                       eps=1e-8, wd=0.01, step, clip_state):
+    """adamw_step with the grad scale and the skip flag read on the device
+    from grad_clip_state's result: a non-finite gradient leaves p, m, v and
+    master untouched."""
+    if p.is_cuda:
+        hip_ops().adamw_step_clipped(p, grad, m, v, master, lr, beta1, beta2,
+                                     eps, wd, step, clip_state)
+    else:
+        reference.adamw_step_clipped(p, grad, m, v, master, lr, beta1, beta2,
+                                     eps, wd, step, clip_state)

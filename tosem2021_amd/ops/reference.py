@@ -165,3 +165,33 @@ def adamw_step(
     vhat = v * bc2
     master.add_(-(lr * (mhat / (vhat.sqrt() + eps) + wd * master)))
     p.copy_(master.to(p.dtype))
+
+
+def grad_clip_state(grad: torch.Tensor, grad_scale: float,
+                    max_norm: float) -> torch.Tensor:
+    """f32[4] = {norm, scale, finite, sumsq} of csrc/grad_norm.hip: the sum
+    of squares accumulates in float64, the state is formed and stored in
+    f32.  norm = grad_scale * sqrt(sumsq) is the norm of the gradient the
+    optimizer sees; scale = grad_scale * min(1, max_norm / (norm + 1e-6))
+    is clip_grad_norm_'s factor folded into the grad scale; finite is 0 when
+    sumsq is inf or NaN in f32."""
+    f32 = torch.float32
+    sumsq64 = grad.detach().double().pow(2).sum().cpu()
+    sumsq = sumsq64.to(f32)
+    gs = torch.tensor(grad_scale, dtype=f32)
+    norm = (gs.double() * sumsq64.sqrt()).to(f32)
+    ratio = torch.tensor(max_norm, dtype=f32) / (norm + 1e-6)
+    one = torch.ones((), dtype=f32)
+    coef = torch.where(ratio < 1, ratio, one)   # a NaN ratio leaves coef at 1
+    finite = torch.isfinite(sumsq).to(f32)
+    return torch.stack([norm, gs * coef, finite, sumsq]).to(grad.device)
+
+
+def adamw_step_clipped(p, grad, m, v, master, lr, beta1, beta2, eps, wd,
+                       step, clip_state) -> None:
+    """adamw_step at the clipped grad scale; a non-finite gradient
+    (clip_state[2] == 0) leaves every buffer untouched."""
+    if float(clip_state[2]) == 0.0:
+        return
+    adamw_step(p, grad, m, v, master, lr, beta1, beta2, eps, wd, step,
+               grad_scale=float(clip_state[1]))

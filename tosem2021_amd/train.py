@@ -78,6 +78,8 @@ class TrainConfig:
     ckpt_dir: Optional[str] = None
     ckpt_every: int = 0          # 0 = only on explicit save()
     ckpt_keep: int = 3           # retain the newest k checkpoints (0 = all)
+    # global-norm gradient clipping + non-finite step skipping; 0 = off
+    max_grad_norm: float = 0.0
 
 
 class Trainer:
@@ -98,8 +100,11 @@ class Trainer:
             # rank-0 init everywhere: broadcast the flat params once
             dist.broadcast(self.flat.flat, src=0)
             self.flat.master.copy_(self.flat.flat.float())
-        self.step_num = 0
+        self.step_num = 0     # attempted steps: LR schedule, checkpoint names
+        self.opt_step = 0     # applied updates: AdamW's bias correction
+        self.skipped_steps = 0
         self.metrics: Dict[str, float] = {}
+        self._clip_state: Optional[torch.Tensor] = None
 
     # ---- schedule -----------------------------------------------------------
     def _lr(self) -> float:
@@ -115,6 +120,44 @@ class Trainer:
         if isinstance(tokens, PackedBatch):
             return self.model(tokens.tokens, attn_mask, packing=tokens)
         return self.model(tokens, attn_mask)
+
+    # ---- optimizer ------------------------------------------------------------
+    def _adamw(self, lr: float, grad_scale: float):
+        """Launch the fused AdamW step; nothing here syncs with the host.
+
+        With cfg.max_grad_norm > 0 the global norm of the averaged gradient
+        is reduced on the device (ops.grad_clip_state) and the clip factor
+        folds into the kernel's grad scale; a non-finite gradient makes the
+        kernel leave every buffer untouched.  _finish_step() reads the
+        outcome back where the step syncs anyway."""
+        f, c = self.flat, self.cfg
+        hp = dict(lr=lr, beta1=c.beta1, beta2=c.beta2, eps=c.eps,
+                  wd=c.weight_decay, step=self.opt_step + 1)
+        if c.max_grad_norm > 0:
+            self._clip_state = ops.grad_clip_state(
+                f.grad_flat, grad_scale=grad_scale, max_norm=c.max_grad_norm)
+            ops.adamw_step_clipped(f.flat, f.grad_flat, f.m, f.v, f.master,
+                                   clip_state=self._clip_state, **hp)
+        else:
+            ops.adamw_step(f.flat, f.grad_flat, f.m, f.v, f.master,
+                           grad_scale=grad_scale, **hp)
+
+    def _finish_step(self) -> dict:
+        """Count the step as applied or skipped; returns the extra
+        observe_step fields (none with clipping off).  Every rank reduces
+        the same all-reduced gradient, so all ranks agree on the outcome."""
+        if self._clip_state is None:
+            self.opt_step += 1
+            return {}
+        norm, _, finite, _ = self._clip_state.tolist()   # the step's one sync
+        self._clip_state = None
+        skipped = finite == 0.0
+        if skipped:
+            self.skipped_steps += 1
+        else:
+            self.opt_step += 1
+        self.metrics["grad_norm"] = norm
+        return {"grad_norm": norm, "skipped": skipped}
 
     # ---- one optimization step ----------------------------------------------
     def step_accum(self, micro_batches) -> float:
@@ -138,13 +181,9 @@ class Trainer:
             self.ddp.finalize()
             self.step_num += 1
             lr = self._lr()
-            ops.adamw_step(
-                self.flat.flat, self.flat.grad_flat, self.flat.m, self.flat.v,
-                self.flat.master, lr=lr, beta1=self.cfg.beta1,
-                beta2=self.cfg.beta2, eps=self.cfg.eps,
-                wd=self.cfg.weight_decay, step=self.step_num,
-                grad_scale=self.ddp.grad_scale / n)
-        get_metrics().observe_step(self.step_num, loss=total_loss / n, lr=lr)
+            self._adamw(lr, self.ddp.grad_scale / n)
+        get_metrics().observe_step(self.step_num, loss=total_loss / n, lr=lr,
+                                   **self._finish_step())
         return total_loss / n
 
     def step(self, tokens, attn_mask: Optional[torch.Tensor],
@@ -159,13 +198,9 @@ class Trainer:
             self.ddp.finalize()
             self.step_num += 1
             lr = self._lr()
-            ops.adamw_step(
-                self.flat.flat, self.flat.grad_flat, self.flat.m, self.flat.v,
-                self.flat.master, lr=lr, beta1=self.cfg.beta1,
-                beta2=self.cfg.beta2, eps=self.cfg.eps, wd=self.cfg.weight_decay,
-                step=self.step_num, grad_scale=self.ddp.grad_scale)
+            self._adamw(lr, self.ddp.grad_scale)
         get_metrics().observe_step(self.step_num, loss=float(loss.detach()),
-                                   lr=lr)
+                                   lr=lr, **self._finish_step())
         if self.cfg.ckpt_every and self.cfg.ckpt_dir and \
                 self.step_num % self.cfg.ckpt_every == 0:
             self.save()
@@ -175,6 +210,8 @@ class Trainer:
     def state_dict(self) -> dict:
         return {
             "step": self.step_num,
+            "opt_step": self.opt_step,
+            "skipped_steps": self.skipped_steps,
             "flat": self.flat.flat,
             "master": self.flat.master,
             "m": self.flat.m,
@@ -214,6 +251,9 @@ class Trainer:
         self.flat.m.copy_(sd["m"])
         self.flat.v.copy_(sd["v"])
         self.step_num = sd["step"]
+        # checkpoints from before step skipping applied every step
+        self.opt_step = sd.get("opt_step", sd["step"])
+        self.skipped_steps = sd.get("skipped_steps", 0)
 
     @staticmethod
     def latest_checkpoint(ckpt_dir: str) -> Optional[str]:
