@@ -239,6 +239,46 @@ __device__ __forceinline__ FaQBlocks fa_qblocks(int L, int wid) {
   return {bid / n_qblocks, qA, qA + FA_QWG};
 }
 
+// ---- folded qkv bias gradient ------------------------------------------------
+// The packed backward's dqkv is the output gradient of the qkv projection,
+// so that projection's bias gradient is the column sum of dqkv over all
+// B * L rows.  Both backward kernels hold their 32-row output tiles in the
+// (register = row, lane = column) layout, so the BIAS instantiations (the
+// others are the kernels without any of this) also emit per workgroup the column sums of the bf16-rounded values it stores:
+// an in-lane chain over the 16 registers, one lane ^ 32 exchange, then the
+// four waves merge through LDS in fixed wave order (no atomics: the result
+// is bitwise reproducible).  bias_ws is [B * ceil(L / 128), bias_ld] f32,
+// bias_ld = 3 * H * 64: one row per 128-row block of a batch element, the
+// q / k / v thirds side by side, 64 columns per head.  Every element is
+// written by exactly one workgroup — rows past L and skipped tiles add
+// exact zeros — and one colsum chain over the rows finishes the sum.
+//
+// The epilogues add bf16_to_f32 of every value they store into one f32 per
+// lane and tile (rows in register order), so the rounding is shared with
+// the store and the extra work is two VALU ops per element; fa_half_merge
+// then adds the other half-wave's rows of the same column.
+__device__ __forceinline__ float fa_half_merge(float s) {
+  return s + __shfl_xor(s, 32, WAVE);
+}
+
+// Merge the waves' sums staged in cs[2][FA_WAVES][64] (wave 0 first) and
+// write the two 64-column results: slot 0 to dst0, slot 1 to dst1 (either
+// may be nullptr).  Threads 0..127; the caller has put a barrier between
+// the staging writes and this.
+__device__ __forceinline__ void fa_colsum_merge_store(const float* cs, int tid,
+                                                      float* dst0,
+                                                      float* dst1) {
+  if (tid < 2 * FA_DH) {
+    const int slot = tid / FA_DH, c = tid % FA_DH;
+    const float* p = cs + slot * FA_WAVES * FA_DH + c;
+    float s = p[0];
+#pragma unroll
+    for (int w = 1; w < FA_WAVES; ++w) s += p[w * FA_DH];
+    float* dst = slot ? dst1 : dst0;
+    if (dst) dst[c] = s;
+  }
+}
+
 // Padding-tail tile skip: with the additive -1e9 padding bias, every score
 // in a fully-masked kv tile sits below ~-1e8 and __expf underflows to
 // exactly +0.0f, so the tile contributes NOTHING to the online softmax
@@ -606,7 +646,7 @@ extern "C" hipError_t flash_fwd_packed_launch(const void* qkv,
 // inside the mirrored fa_seg_range of the workgroup's 128 kv rows are
 // visited.  SEG excludes mask and the dS output.
 
-template <bool SEG>
+template <bool SEG, bool BIAS>
 __global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
                        const short* __restrict__ v,
@@ -617,7 +657,8 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
                        const float* __restrict__ ddot,
                        short* __restrict__ ds, short* __restrict__ dk,
                        short* __restrict__ dv,
-                       int B, int H, int L, float scale, FaGeom g) {
+                       int B, int H, int L, float scale, FaGeom g,
+                       float* __restrict__ bias_ws, int bias_ld) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   short* q_lds = (short*)smem;
   short* do_lds = (short*)(smem + TILE_LDS_BYTES);
@@ -792,6 +833,7 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   }   // !skip_tile
 
   // epilogue: dV/dK rows of this wave's kv block (reg=kv row, lane=d col)
+  float csk[2] = {0.f, 0.f}, csv[2] = {0.f, 0.f};   // BIAS: column sums
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
 #pragma unroll
@@ -799,9 +841,36 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
       int kvl = c_row(r, half);
       if (kv_base + kvl >= L) continue;
       long off = qkv_off + (long)(kv_base + kvl) * g.qkv_rs + 32 * t + col;
-      dv[off] = f32_to_bf16(dv_acc[t][r]);
-      dk[off] = f32_to_bf16(dk_acc[t][r]);
+      const short vb = f32_to_bf16(dv_acc[t][r]);
+      const short kb16 = f32_to_bf16(dk_acc[t][r]);
+      dv[off] = vb;
+      dk[off] = kb16;
+      if constexpr (BIAS) {   // the sum of what is STORED
+        csv[t] += bf16_to_f32(vb);
+        csk[t] += bf16_to_f32(kb16);
+      }
     }
+  }
+  // folded bias gradient: this workgroup's k and v columns of its ws row.
+  // The barriers are unconditional, so workgroup-uniform; skip_tile and
+  // wave_skip arrive here with exact-zero accumulators, rows past L add
+  // nothing.
+  if constexpr (BIAS) {
+    float* cs = (float*)smem;        // [2][FA_WAVES][64]: dK, dV
+    __syncthreads();                 // every wave is done with the tiles
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float sk_ = fa_half_merge(csk[t]);
+      float sv_ = fa_half_merge(csv[t]);
+      if (half == 0) {
+        cs[(0 * FA_WAVES + wid) * FA_DH + 32 * t + col] = sk_;
+        cs[(1 * FA_WAVES + wid) * FA_DH + 32 * t + col] = sv_;
+      }
+    }
+    __syncthreads();
+    const int third = bias_ld / 3;
+    float* row = bias_ws + ((long)b * n_kvblocks + kb) * bias_ld + h * FA_DH;
+    fa_colsum_merge_store(cs, tid, row + third, row + 2 * third);
   }
 }
 
@@ -810,19 +879,32 @@ static void fa_bwd_fused_dispatch(const short* q, const short* k,
                                   const void* mask, const void* seg,
                                   const void* lse, const void* ddot, void* ds,
                                   short* dk, short* dv, int B, int H, int L,
-                                  float scale, FaGeom g, hipStream_t stream) {
+                                  float scale, FaGeom g, float* bias_ws,
+                                  hipStream_t stream) {
   const dim3 grid = fa_grid(B, H, L, FA_QWG);
-  if (seg)
-    flash_bwd_fused_kernel<true><<<grid, FA_BLOCK, BWD_SEG_LDS_BYTES,
-                                   stream>>>(
-        q, k, v, (const short*)dout, nullptr, (const int*)seg,
-        (const float*)lse, (const float*)ddot, nullptr, dk, dv, B, H, L,
-        scale, g);
-  else
-    flash_bwd_fused_kernel<false><<<grid, FA_BLOCK, BWD_LDS_BYTES, stream>>>(
-        q, k, v, (const short*)dout, (const float*)mask, nullptr,
-        (const float*)lse, (const float*)ddot, (short*)ds, dk, dv, B, H, L,
-        scale, g);
+  const int bias_ld = 3 * H * FA_DH;
+#define FA_BWD_SEG_ARGS                                                       \
+  q, k, v, (const short*)dout, nullptr, (const int*)seg, (const float*)lse,   \
+      (const float*)ddot, nullptr, dk, dv, B, H, L, scale, g, bias_ws, bias_ld
+#define FA_BWD_ARGS                                                           \
+  q, k, v, (const short*)dout, (const float*)mask, nullptr,                   \
+      (const float*)lse, (const float*)ddot, (short*)ds, dk, dv, B, H, L,     \
+      scale, g, bias_ws, bias_ld
+  if (seg && bias_ws) {
+    flash_bwd_fused_kernel<true, true><<<grid, FA_BLOCK, BWD_SEG_LDS_BYTES,
+                                         stream>>>(FA_BWD_SEG_ARGS);
+  } else if (seg) {
+    flash_bwd_fused_kernel<true, false><<<grid, FA_BLOCK, BWD_SEG_LDS_BYTES,
+                                          stream>>>(FA_BWD_SEG_ARGS);
+  } else if (bias_ws) {
+    flash_bwd_fused_kernel<false, true><<<grid, FA_BLOCK, BWD_LDS_BYTES,
+                                          stream>>>(FA_BWD_ARGS);
+  } else {
+    flash_bwd_fused_kernel<false, false><<<grid, FA_BLOCK, BWD_LDS_BYTES,
+                                           stream>>>(FA_BWD_ARGS);
+  }
+#undef FA_BWD_ARGS
+#undef FA_BWD_SEG_ARGS
 }
 
 // seg excludes the dS output: with seg given, ds must be nullptr
@@ -835,20 +917,23 @@ extern "C" hipError_t flash_bwd_fused_launch(
   fa_bwd_fused_dispatch((const short*)q, (const short*)k, (const short*)v,
                         dout, mask, seg, lse, ddot, ds, (short*)dk,
                         (short*)dv, B, H, L, scale, FaGeom::bhld(H, L),
-                        stream);
+                        nullptr, stream);
   return hipGetLastError();
 }
 
-// packed: qkv/dqkv [B, L, 3D], dout [B, L, D]; dk/dv land inside dqkv
+// packed: qkv/dqkv [B, L, 3D], dout [B, L, D]; dk/dv land inside dqkv.
+// bias_ws (optional): [B * ceil(L / 128), 3D] f32 column partials, the k and
+// v thirds are written here.
 extern "C" hipError_t flash_bwd_fused_packed_launch(
     const void* qkv, const void* dout, const void* mask, const void* seg,
-    const void* lse, const void* ddot, void* dqkv, int B, int H, int L,
-    float scale, hipStream_t stream) {
+    const void* lse, const void* ddot, void* dqkv, void* bias_ws, int B,
+    int H, int L, float scale, hipStream_t stream) {
   const int D = H * FA_DH;
   fa_bwd_fused_dispatch((const short*)qkv, (const short*)qkv + D,
                         (const short*)qkv + 2 * D, dout, mask, seg, lse, ddot,
                         nullptr, (short*)dqkv + D, (short*)dqkv + 2 * D, B, H,
-                        L, scale, FaGeom::packed(H, L), stream);
+                        L, scale, FaGeom::packed(H, L), (float*)bias_ws,
+                        stream);
   return hipGetLastError();
 }
 
@@ -959,7 +1044,7 @@ extern "C" hipError_t flash_dq_launch(const void* ds, const void* k, void* dq,
 //   dQ[q, d] += mfma(dS-frag, K^T-frag), K^T gathered from the staged K tile
 // Segmented (SEG): as in flash_fwd — q ids lane-local, kv ids per register,
 // kv tiles limited to the workgroup's fa_seg_range.
-template <bool SEG>
+template <bool SEG, bool BIAS>
 __global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_dq_recompute_kernel(const short* __restrict__ q,
                           const short* __restrict__ k,
@@ -970,7 +1055,8 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
                           const float* __restrict__ lse,
                           const float* __restrict__ ddot,
                           short* __restrict__ dq,
-                          int B, int H, int L, float scale, FaGeom g) {
+                          int B, int H, int L, float scale, FaGeom g,
+                          float* __restrict__ bias_ws, int bias_ld) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   short* k_lds = (short*)smem;
   short* v_lds = (short*)(smem + TILE_LDS_BYTES);
@@ -1117,19 +1203,46 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   }
 
   // ---- epilogue ----
+  float csA[2] = {0.f, 0.f}, csB[2] = {0.f, 0.f};   // BIAS: column sums
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int rloc = c_row(r, half);
       int qA = qb.qA + rloc, qB = qb.qB + rloc;
-      if (qA < L)
-        dq[qkv_off + (long)qA * g.qkv_rs + 32 * t + col] =
-            f32_to_bf16(dqA[t][r]);
-      if (qB < L)
-        dq[qkv_off + (long)qB * g.qkv_rs + 32 * t + col] =
-            f32_to_bf16(dqB[t][r]);
+      if (qA < L) {
+        const short a16 = f32_to_bf16(dqA[t][r]);
+        dq[qkv_off + (long)qA * g.qkv_rs + 32 * t + col] = a16;
+        if constexpr (BIAS) csA[t] += bf16_to_f32(a16);   // what is STORED
+      }
+      if (qB < L) {
+        const short b16 = f32_to_bf16(dqB[t][r]);
+        dq[qkv_off + (long)qB * g.qkv_rs + 32 * t + col] = b16;
+        if constexpr (BIAS) csB[t] += bf16_to_f32(b16);
+      }
     }
+  }
+  // folded bias gradient: the q columns of the two 128-row blocks this
+  // workgroup covers (the waves' A blocks, then their B blocks).  The
+  // barriers are unconditional, so workgroup-uniform.
+  if constexpr (BIAS) {
+    float* cs = (float*)smem;        // [2][FA_WAVES][64]: blocks A, B
+    __syncthreads();                 // every wave is done with the tiles
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float sA_ = fa_half_merge(csA[t]);
+      float sB_ = fa_half_merge(csB[t]);
+      if (half == 0) {
+        cs[(0 * FA_WAVES + wid) * FA_DH + 32 * t + col] = sA_;
+        cs[(1 * FA_WAVES + wid) * FA_DH + 32 * t + col] = sB_;
+      }
+    }
+    __syncthreads();
+    const int n128 = (L + FA_QWG - 1) / FA_QWG;
+    const int blkA = (qb.qA - wid * FA_QB) / FA_QWG;   // workgroup-uniform
+    float* row = bias_ws + ((long)b * n128 + blkA) * bias_ld + h * FA_DH;
+    fa_colsum_merge_store(cs, tid, row,
+                          blkA + 1 < n128 ? row + bias_ld : nullptr);
   }
 }
 
@@ -1138,19 +1251,32 @@ static void fa_dq_recompute_dispatch(const short* q, const short* k,
                                      const void* mask, const void* seg,
                                      const void* lse, const void* ddot,
                                      void* dq, int B, int H, int L,
-                                     float scale, FaGeom g,
+                                     float scale, FaGeom g, float* bias_ws,
                                      hipStream_t stream) {
   const dim3 grid = fa_grid(B, H, L, FA_Q2WG);
-  if (seg)
-    flash_dq_recompute_kernel<true><<<grid, FA_BLOCK, DQR_LDS_BYTES,
-                                      stream>>>(
-        q, k, v, (const short*)dout, nullptr, (const int*)seg,
-        (const float*)lse, (const float*)ddot, (short*)dq, B, H, L, scale, g);
-  else
-    flash_dq_recompute_kernel<false><<<grid, FA_BLOCK, DQR_LDS_BYTES,
-                                       stream>>>(
-        q, k, v, (const short*)dout, (const float*)mask, nullptr,
-        (const float*)lse, (const float*)ddot, (short*)dq, B, H, L, scale, g);
+  const int bias_ld = 3 * H * FA_DH;
+#define FA_DQR_SEG_ARGS                                                       \
+  q, k, v, (const short*)dout, nullptr, (const int*)seg, (const float*)lse,   \
+      (const float*)ddot, (short*)dq, B, H, L, scale, g, bias_ws, bias_ld
+#define FA_DQR_ARGS                                                           \
+  q, k, v, (const short*)dout, (const float*)mask, nullptr,                   \
+      (const float*)lse, (const float*)ddot, (short*)dq, B, H, L, scale, g,   \
+      bias_ws, bias_ld
+  if (seg && bias_ws) {
+    flash_dq_recompute_kernel<true, true><<<grid, FA_BLOCK, DQR_LDS_BYTES,
+                                            stream>>>(FA_DQR_SEG_ARGS);
+  } else if (seg) {
+    flash_dq_recompute_kernel<true, false><<<grid, FA_BLOCK, DQR_LDS_BYTES,
+                                             stream>>>(FA_DQR_SEG_ARGS);
+  } else if (bias_ws) {
+    flash_dq_recompute_kernel<false, true><<<grid, FA_BLOCK, DQR_LDS_BYTES,
+                                             stream>>>(FA_DQR_ARGS);
+  } else {
+    flash_dq_recompute_kernel<false, false><<<grid, FA_BLOCK, DQR_LDS_BYTES,
+                                              stream>>>(FA_DQR_ARGS);
+  }
+#undef FA_DQR_ARGS
+#undef FA_DQR_SEG_ARGS
 }
 
 extern "C" hipError_t flash_dq_recompute_launch(
@@ -1159,20 +1285,21 @@ extern "C" hipError_t flash_dq_recompute_launch(
     void* dq, int B, int H, int L, float scale, hipStream_t stream) {
   fa_dq_recompute_dispatch((const short*)q, (const short*)k, (const short*)v,
                            dout, mask, seg, lse, ddot, dq, B, H, L, scale,
-                           FaGeom::bhld(H, L), stream);
+                           FaGeom::bhld(H, L), nullptr, stream);
   return hipGetLastError();
 }
 
-// packed: dq lands in the q third of dqkv [B, L, 3D]
+// packed: dq lands in the q third of dqkv [B, L, 3D]; bias_ws (optional) as
+// in flash_bwd_fused_packed_launch, the q third is written here.
 extern "C" hipError_t flash_dq_recompute_packed_launch(
     const void* qkv, const void* dout, const void* mask, const void* seg,
-    const void* lse, const void* ddot, void* dqkv, int B, int H, int L,
-    float scale, hipStream_t stream) {
+    const void* lse, const void* ddot, void* dqkv, void* bias_ws, int B,
+    int H, int L, float scale, hipStream_t stream) {
   const int D = H * FA_DH;
   fa_dq_recompute_dispatch((const short*)qkv, (const short*)qkv + D,
                            (const short*)qkv + 2 * D, dout, mask, seg, lse,
                            ddot, dqkv, B, H, L, scale, FaGeom::packed(H, L),
-                           stream);
+                           (float*)bias_ws, stream);
   return hipGetLastError();
 }
 

@@ -235,20 +235,60 @@ ln_fwd_t(const short* __restrict__ x, const short* __restrict__ res,
   }
 }
 
-// Deterministic by construction: dgamma/dbeta partials accumulate in
-// registers (each (wave, lane, j) owns a fixed column set) and every wave
-// writes its OWN ws row — no LDS, no atomics, no cross-wave float-order
-// dependence (the earlier LDS-atomicAdd merge was caught non-deterministic
-// by test_kernels_bitwise_deterministic).  ws has gridDim.x * WAVES_PER_BLOCK
-// rows; the two-stage colsum reduces them in fixed order.
-template <int PKTS, bool HASDE>
+// Column partials of the LayerNorm backward.  Every backward kernel writes
+// ONE f32 workspace row of NOUT * D floats per block (per wave on the wide
+// path): [dgamma | dbeta] and, with DRES, a third slab [dres_sum] — the
+// column sum of the bf16-rounded dx values the kernel stores, which is the
+// bias gradient of the projection that fed this LayerNorm's residual input.
+// A single colsum chain over width NOUT * D then reduces all of them.
+//
+// Fixed-order merge of a block's four waves through LDS, wave 0 first: every
+// column is summed in the same order on every run, with no atomics (an
+// LDS-atomicAdd merge was caught non-deterministic by
+// test_kernels_bitwise_deterministic).  Lane l owns columns
+// (p * 64 + l) * 8 + j of every slab; all four barriers are block-uniform.
+template <int PKTS, int NOUT>
+__device__ __forceinline__ void ln_bwd_merge_store(
+    const float (&acc)[NOUT][PKTS * 8], float* __restrict__ sm,
+    float* __restrict__ ws, int lane, int wid) {
+  constexpr int DT = PKTS * WAVE * 8;
+  for (int w = 0; w < WAVES_PER_BLOCK; ++w) {
+    if (wid == w) {
+#pragma unroll
+      for (int o = 0; o < NOUT; ++o) {
+#pragma unroll
+        for (int p = 0; p < PKTS; ++p) {
+          float4_t* s4 = (float4_t*)(sm + o * DT + (p * WAVE + lane) * 8);
+          float4_t a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+          if (w) { a = s4[0]; b = s4[1]; }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            a[j] += acc[o][p * 8 + j];
+            b[j] += acc[o][p * 8 + 4 + j];
+          }
+          s4[0] = a; s4[1] = b;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  float* orow = ws + (long)blockIdx.x * (NOUT * DT);
+  for (int i = threadIdx.x * 4; i < NOUT * DT; i += BLOCK * 4)
+    *(float4_t*)(orow + i) = *(const float4_t*)(sm + i);
+}
+
+// One row per wave; partials accumulate in registers (each (wave, lane, j)
+// owns a fixed column set) and merge per block as above.  ws has gridDim.x
+// rows; the colsum reduces them in fixed order.
+template <int PKTS, bool HASDE, bool DRES>
 __global__ void __launch_bounds__(BLOCK)
 ln_bwd_t(const short* __restrict__ dy, const short* __restrict__ x,
          const short* __restrict__ gamma, const float* __restrict__ mean_in,
          const float* __restrict__ rstd_in,
          const short* __restrict__ ds_extra, short* __restrict__ dx,
-         float* __restrict__ ws_dgamma, float* __restrict__ ws_dbeta,
-         int N, int D) {
+         float* __restrict__ ws, int N, int D) {
+  constexpr int NOUT = DRES ? 3 : 2;
+  __shared__ __attribute__((aligned(16))) float sm[NOUT * PKTS * WAVE * 8];
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   float gv[PKTS * 8];
@@ -258,7 +298,7 @@ ln_bwd_t(const short* __restrict__ dy, const short* __restrict__ x,
 #pragma unroll
     for (int j = 0; j < 8; ++j) gv[p * 8 + j] = bf16_to_f32(g8[j]);
   }
-  float dg_acc[PKTS * 8] = {0.f}, db_acc[PKTS * 8] = {0.f};
+  float acc[NOUT][PKTS * 8] = {{0.f}};  // [dgamma, dbeta, dres_sum]
   const int rstride = gridDim.x * WAVES_PER_BLOCK;
   int row = blockIdx.x * WAVES_PER_BLOCK + wid;
   const bool active = row < N;
@@ -287,8 +327,8 @@ ln_bwd_t(const short* __restrict__ dy, const short* __restrict__ x,
         float g = d * gv[k];
         if (HASDE) ev[k] = bf16_to_f32(ve[p][j]);
         xh[k] = h; dyg[k] = g;
-        dg_acc[k] += d * h;
-        db_acc[k] += d;
+        acc[0][k] += d * h;
+        acc[1][k] += d;
         s1 += g; s2 += g * h;
       }
     }
@@ -312,24 +352,15 @@ ln_bwd_t(const short* __restrict__ dy, const short* __restrict__ x,
         float d_ = rstd * (dyg[k] - s1 - xh[k] * s2);
         if (HASDE) d_ += ev[k];
         o[j] = f32_to_bf16(d_);
+        // the sum of what is STORED: round first, then accumulate
+        if (DRES) acc[NOUT - 1][k] += bf16_to_f32(o[j]);
       }
       *(short8_t*)(dx + (long)row * D + (p * WAVE + lane) * 8) = o;
     }
     if (next >= N) break;
     row = next;
   }
-  float* og = ws_dgamma +
-              (long)(blockIdx.x * WAVES_PER_BLOCK + wid) * D;
-  float* ob = ws_dbeta + (long)(blockIdx.x * WAVES_PER_BLOCK + wid) * D;
-#pragma unroll
-  for (int p = 0; p < PKTS; ++p) {
-    int base = (p * WAVE + lane) * 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      og[base + j] = dg_acc[p * 8 + j];
-      ob[base + j] = db_acc[p * 8 + j];
-    }
-  }
+  ln_bwd_merge_store<PKTS, NOUT>(acc, sm, ws, lane, wid);
 }
 
 // Two rows per wave (round 2): the single-row ln_bwd_t is latency-bound on
@@ -337,16 +368,17 @@ ln_bwd_t(const short* __restrict__ dy, const short* __restrict__ x,
 // per row; measured ~2-3 TB/s vs ln_fwd's 6.4).  Interleaving two
 // independent rows per wave doubles the work inside the same latency
 // shadow — the four wave_sum chains (s1/s2 x 2 rows) issue back-to-back.
-// dgamma/dbeta accumulators are shared (summed over both rows), so the
-// per-wave ws row layout and the deterministic colsum are unchanged.
-template <int PKTS, bool HASDE>
+// The column accumulators are shared (summed over both rows, row A first), so
+// the workspace layout and the deterministic colsum are unchanged.
+template <int PKTS, bool HASDE, bool DRES>
 __global__ void __launch_bounds__(BLOCK)
 ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
           const short* __restrict__ gamma, const float* __restrict__ mean_in,
           const float* __restrict__ rstd_in,
           const short* __restrict__ ds_extra, short* __restrict__ dx,
-          float* __restrict__ ws_dgamma, float* __restrict__ ws_dbeta,
-          int N, int D) {
+          float* __restrict__ ws, int N, int D) {
+  constexpr int NOUT = DRES ? 3 : 2;
+  __shared__ __attribute__((aligned(16))) float sm[NOUT * PKTS * WAVE * 8];
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   float gv[PKTS * 8];
@@ -356,7 +388,7 @@ ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
 #pragma unroll
     for (int j = 0; j < 8; ++j) gv[p * 8 + j] = bf16_to_f32(g8[j]);
   }
-  float dg_acc[PKTS * 8] = {0.f}, db_acc[PKTS * 8] = {0.f};
+  float acc[NOUT][PKTS * 8] = {{0.f}};  // [dgamma, dbeta, dres_sum]
   const int rstride = gridDim.x * WAVES_PER_BLOCK * 2;
   int rowA = (blockIdx.x * WAVES_PER_BLOCK + wid) * 2;
   short8_t vdA[PKTS], vxA[PKTS], veA[PKTS];
@@ -394,16 +426,16 @@ ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
         float hA = (bf16_to_f32(vxA[p][j]) - meanA) * rstdA;
         float gA = dA * gv[k];
         xhA[k] = hA; dygA[k] = gA;
-        dg_acc[k] += dA * hA;
-        db_acc[k] += dA;
+        acc[0][k] += dA * hA;
+        acc[1][k] += dA;
         s1A += gA; s2A += gA * hA;
         if (actB) {
           float dB = bf16_to_f32(vdB[p][j]);
           float hB = (bf16_to_f32(vxB[p][j]) - meanB) * rstdB;
           float gB = dB * gv[k];
           xhB[k] = hB; dygB[k] = gB;
-          dg_acc[k] += dB * hB;
-          db_acc[k] += dB;
+          acc[0][k] += dB * hB;
+          acc[1][k] += dB;
           s1B += gB; s2B += gB * hB;
         }
       }
@@ -435,10 +467,13 @@ ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
         float dA_ = rstdA * (dygA[k] - s1A - xhA[k] * s2A);
         if (HASDE) dA_ += bf16_to_f32(veA[p][j]);
         oA[j] = f32_to_bf16(dA_);
+        // the sum of what is STORED: round first, then accumulate
+        if (DRES) acc[NOUT - 1][k] += bf16_to_f32(oA[j]);
         if (actB) {
           float dB_ = rstdB * (dygB[k] - s1B - xhB[k] * s2B);
           if (HASDE) dB_ += bf16_to_f32(veB[p][j]);
           oB[j] = f32_to_bf16(dB_);
+          if (DRES) acc[NOUT - 1][k] += bf16_to_f32(oB[j]);
         }
       }
       int base = (p * WAVE + lane) * 8;
@@ -458,17 +493,7 @@ ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
       }
     }
   }
-  float* og = ws_dgamma + (long)(blockIdx.x * WAVES_PER_BLOCK + wid) * D;
-  float* ob = ws_dbeta + (long)(blockIdx.x * WAVES_PER_BLOCK + wid) * D;
-#pragma unroll
-  for (int p = 0; p < PKTS; ++p) {
-    int base = (p * WAVE + lane) * 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      og[base + j] = dg_acc[p * 8 + j];
-      ob[base + j] = db_acc[p * 8 + j];
-    }
-  }
+  ln_bwd_merge_store<PKTS, NOUT>(acc, sm, ws, lane, wid);
 }
 
 // General-width backward, any D % 8 == 0 up to MAXP * 512 (the widths
@@ -478,22 +503,20 @@ ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
 // row loop, so the row and the dgamma/dbeta partials stay in registers.
 // The four waves of a block then merge their partials through LDS one wave
 // at a time, wave 0 first: every column is summed in the same order on
-// every run, with no atomics.  One ws row per block.
-template <int MAXP>
+// every run, with no atomics.  One ws row of NOUT * D floats per block.
+template <int MAXP, bool DRES>
 __global__ void __launch_bounds__(BLOCK)
 ln_bwd_g(const short* __restrict__ dy, const short* __restrict__ x,
          const short* __restrict__ gamma, const float* __restrict__ mean_in,
          const float* __restrict__ rstd_in,
          const short* __restrict__ ds_extra,  // optional += into dx
-         short* __restrict__ dx,
-         float* __restrict__ ws_dgamma, float* __restrict__ ws_dbeta,
-         int N, int D) {
+         short* __restrict__ dx, float* __restrict__ ws, int N, int D) {
+  constexpr int NOUT = DRES ? 3 : 2;
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sg = (float*)smem;          // [D] dgamma partial for this block
-  float* sb = sg + D;                // [D] dbeta partial
-  float dg_acc[MAXP * 8] = {0.f}, db_acc[MAXP * 8] = {0.f};
+  float* sm = (float*)smem;  // [NOUT, D] partials of this block
+  float acc[NOUT][MAXP * 8] = {{0.f}};  // [dgamma, dbeta, dres_sum]
   for (int row = blockIdx.x * WAVES_PER_BLOCK + wid; row < N;
        row += gridDim.x * WAVES_PER_BLOCK) {
     const short* dyr = dy + (long)row * D;
@@ -515,8 +538,8 @@ ln_bwd_g(const short* __restrict__ dy, const short* __restrict__ x,
         float d = bf16_to_f32(vd[p][j]);
         float h = (bf16_to_f32(vx[p][j]) - mean) * rstd;
         float g = d * bf16_to_f32(vg[p][j]);
-        dg_acc[p * 8 + j] += d * h;
-        db_acc[p * 8 + j] += d;
+        acc[0][p * 8 + j] += d * h;
+        acc[1][p * 8 + j] += d;
         s1 += g; s2 += g * h;
       }
     }
@@ -536,6 +559,8 @@ ln_bwd_g(const short* __restrict__ dy, const short* __restrict__ x,
         float d_ = rstd * (g - s1 - h * s2);
         if (der) d_ += bf16_to_f32(ev[j]);
         o[j] = f32_to_bf16(d_);
+        // the sum of what is STORED: round first, then accumulate
+        if (DRES) acc[NOUT - 1][p * 8 + j] += bf16_to_f32(o[j]);
       }
       *(short8_t*)(dxr + base) = o;
     }
@@ -545,22 +570,24 @@ ln_bwd_g(const short* __restrict__ dy, const short* __restrict__ x,
   for (int w = 0; w < WAVES_PER_BLOCK; ++w) {
     if (wid == w) {
 #pragma unroll
-      for (int p = 0; p < MAXP; ++p) {
-        int base = (p * WAVE + lane) * 8;
-        if (base >= D) continue;
+      for (int o = 0; o < NOUT; ++o) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float pg = w ? sg[base + j] : 0.f, pb = w ? sb[base + j] : 0.f;
-          sg[base + j] = pg + dg_acc[p * 8 + j];
-          sb[base + j] = pb + db_acc[p * 8 + j];
+        for (int p = 0; p < MAXP; ++p) {
+          int base = (p * WAVE + lane) * 8;
+          if (base >= D) continue;
+          float* so = sm + o * D;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float prev = w ? so[base + j] : 0.f;
+            so[base + j] = prev + acc[o][p * 8 + j];
+          }
         }
       }
     }
     __syncthreads();
   }
-  float* og = ws_dgamma + (long)blockIdx.x * D;
-  float* ob = ws_dbeta + (long)blockIdx.x * D;
-  for (int i = threadIdx.x; i < D; i += BLOCK) { og[i] = sg[i]; ob[i] = sb[i]; }
+  float* orow = ws + (long)blockIdx.x * (NOUT * D);
+  for (int i = threadIdx.x; i < NOUT * D; i += BLOCK) orow[i] = sm[i];
 }
 
 // Widths above LN_BWD_G_MAX_D: the partials no longer fit in registers, so
@@ -569,21 +596,27 @@ ln_bwd_g(const short* __restrict__ dy, const short* __restrict__ x,
 // no atomics), and the colsum reduces the gridDim.x * WAVES_PER_BLOCK rows in
 // fixed order like the template path's.
 #define LN_BWD_G_MAX_D 4096
+template <bool DRES>
 __global__ void __launch_bounds__(BLOCK)
 ln_bwd_wide_kernel(const short* __restrict__ dy, const short* __restrict__ x,
                    const short* __restrict__ gamma,
                    const float* __restrict__ mean_in,
                    const float* __restrict__ rstd_in,
                    const short* __restrict__ ds_extra,
-                   short* __restrict__ dx, float* __restrict__ ws_dgamma,
-                   float* __restrict__ ws_dbeta, int N, int D) {
+                   short* __restrict__ dx, float* __restrict__ ws, int N,
+                   int D) {
+  constexpr int NOUT = DRES ? 3 : 2;
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
-  float* og = ws_dgamma + (long)(blockIdx.x * WAVES_PER_BLOCK + wid) * D;
-  float* ob = ws_dbeta + (long)(blockIdx.x * WAVES_PER_BLOCK + wid) * D;
+  float* og = ws + (long)(blockIdx.x * WAVES_PER_BLOCK + wid) * (NOUT * D);
+  float* ob = og + D;
+  float* od = og + (NOUT - 1) * D;  // dres_sum slab (DRES only)
   for (int i = lane * 8; i < D; i += WAVE * 8) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { og[i + j] = 0.f; ob[i + j] = 0.f; }
+    for (int j = 0; j < 8; ++j) {
+      og[i + j] = 0.f; ob[i + j] = 0.f;
+      if (DRES) od[i + j] = 0.f;
+    }
   }
   for (int row = blockIdx.x * WAVES_PER_BLOCK + wid; row < N;
        row += gridDim.x * WAVES_PER_BLOCK) {
@@ -623,6 +656,7 @@ ln_bwd_wide_kernel(const short* __restrict__ dy, const short* __restrict__ x,
         o[j] = f32_to_bf16(d_);
         og[i + j] += d * h;
         ob[i + j] += d;
+        if (DRES) od[i + j] += bf16_to_f32(o[j]);
       }
       *(short8_t*)(dxr + i) = o;
     }
@@ -649,6 +683,26 @@ colsum_stage_kernel(const float* __restrict__ ws, float* __restrict__ out,
     for (int j = 0; j < 4; ++j) s[j] += v[j];
   }
   *(float4_t*)(out + (long)blockIdx.y * D + col) = s;
+}
+
+// Final stage of the chain for callers that want bf16: the same sum over
+// all R rows in the same order, rounded once on the way out, so the
+// parameter gradient needs no separate convert launch.
+__global__ void __launch_bounds__(256)
+colsum_stage_bf16_kernel(const float* __restrict__ ws, short* __restrict__ out,
+                         int R, int D) {
+  int col = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (col >= D) return;
+  float4_t s = {0.f, 0.f, 0.f, 0.f};
+  for (int r = 0; r < R; ++r) {
+    float4_t v = *(const float4_t*)(ws + (long)r * D + col);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] += v[j];
+  }
+  short4_t o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = f32_to_bf16(s[j]);
+  *(short4_t*)(out + col) = o;
 }
 
 // Bias gradient: column-sum of a [N, D] bf16 matrix -> [D] bf16.
@@ -758,64 +812,68 @@ static int ln_bwd_use_1row() {
   return v;
 }
 
+// ws is [ln_bwd_ws_rows(D, grid), n_out * D] f32 with n_out = 2
+// ([dgamma | dbeta]) or 3 (+ [dres_sum]); every width supports both.
 hipError_t ln_bwd_launch(const void* dy, const void* x, const void* gamma,
                          const void* mean, const void* rstd,
-                         const void* ds_extra, void* dx,
-                         void* ws_dgamma, void* ws_dbeta, int N, int D,
-                         int grid, hipStream_t stream) {
-  size_t shm = (size_t)D * 2 * sizeof(float);
+                         const void* ds_extra, void* dx, void* ws, int n_out,
+                         int N, int D, int grid, hipStream_t stream) {
+  if (n_out != 2 && n_out != 3) return hipErrorInvalidValue;
+  const bool dres = n_out == 3;
+  size_t shm = (size_t)D * n_out * sizeof(float);
+#define LNB_ARGS                                                              \
+  (const short*)dy, (const short*)x, (const short*)gamma, (const float*)mean, \
+      (const float*)rstd, (const short*)ds_extra, (short*)dx, (float*)ws, N, D
+#define LNB_K(K, P)                                                           \
+  do {                                                                        \
+    if (ds_extra && dres) {                                                   \
+      K<P, true, true><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);                 \
+    } else if (ds_extra) {                                                    \
+      K<P, true, false><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);                \
+    } else if (dres) {                                                        \
+      K<P, false, true><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);                \
+    } else {                                                                  \
+      K<P, false, false><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);               \
+    }                                                                         \
+  } while (0)
 #define LNB_T(P)                                                              \
   do {                                                                        \
     if (ln_bwd_use_1row()) {                                                  \
-      if (ds_extra)                                                           \
-        ln_bwd_t<P, true><<<grid, BLOCK, 0, stream>>>(                        \
-            (const short*)dy, (const short*)x, (const short*)gamma,           \
-            (const float*)mean, (const float*)rstd, (const short*)ds_extra,   \
-            (short*)dx, (float*)ws_dgamma, (float*)ws_dbeta, N, D);           \
-      else                                                                    \
-        ln_bwd_t<P, false><<<grid, BLOCK, 0, stream>>>(                       \
-            (const short*)dy, (const short*)x, (const short*)gamma,           \
-            (const float*)mean, (const float*)rstd, nullptr, (short*)dx,      \
-            (float*)ws_dgamma, (float*)ws_dbeta, N, D);                       \
-      break;                                                                  \
+      LNB_K(ln_bwd_t, P);                                                     \
+    } else {                                                                  \
+      LNB_K(ln_bwd_t2, P);                                                    \
     }                                                                         \
-    if (ds_extra)                                                             \
-      ln_bwd_t2<P, true><<<grid, BLOCK, 0, stream>>>(                         \
-          (const short*)dy, (const short*)x, (const short*)gamma,             \
-          (const float*)mean, (const float*)rstd, (const short*)ds_extra,     \
-          (short*)dx, (float*)ws_dgamma, (float*)ws_dbeta, N, D);             \
-    else                                                                      \
-      ln_bwd_t2<P, false><<<grid, BLOCK, 0, stream>>>(                        \
-          (const short*)dy, (const short*)x, (const short*)gamma,             \
-          (const float*)mean, (const float*)rstd, nullptr, (short*)dx,        \
-          (float*)ws_dgamma, (float*)ws_dbeta, N, D);                         \
   } while (0)
 #define LNB_G(P)                                                              \
-  ln_bwd_g<P><<<grid, BLOCK, shm, stream>>>(                                  \
-      (const short*)dy, (const short*)x, (const short*)gamma,                 \
-      (const float*)mean, (const float*)rstd, (const short*)ds_extra,         \
-      (short*)dx, (float*)ws_dgamma, (float*)ws_dbeta, N, D)
+  do {                                                                        \
+    if (dres) {                                                               \
+      ln_bwd_g<P, true><<<grid, BLOCK, shm, stream>>>(LNB_ARGS);              \
+    } else {                                                                  \
+      ln_bwd_g<P, false><<<grid, BLOCK, shm, stream>>>(LNB_ARGS);             \
+    }                                                                         \
+  } while (0)
   if (D == 512) LNB_T(1);
   else if (D == 1024) LNB_T(2);
   else if (D <= 512) LNB_G(1);
   else if (D <= 1024) LNB_G(2);
   else if (D <= 2048) LNB_G(4);
   else if (D <= LN_BWD_G_MAX_D) LNB_G(8);
-  else
-    ln_bwd_wide_kernel<<<grid, BLOCK, 0, stream>>>(
-        (const short*)dy, (const short*)x, (const short*)gamma,
-        (const float*)mean, (const float*)rstd, (const short*)ds_extra,
-        (short*)dx, (float*)ws_dgamma, (float*)ws_dbeta, N, D);
+  else if (dres) {
+    ln_bwd_wide_kernel<true><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);
+  } else {
+    ln_bwd_wide_kernel<false><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);
+  }
 #undef LNB_G
 #undef LNB_T
+#undef LNB_K
+#undef LNB_ARGS
   return hipGetLastError();
 }
 
 // Workspace rows ln_bwd_launch writes for a grid of `grid` blocks: one per
-// wave on the template and wide paths, one per block on the general path.
+// block (the waves merge through LDS), one per wave on the wide path.
 int ln_bwd_ws_rows(int D, int grid) {
-  const bool per_wave = D == 512 || D == 1024 || D > LN_BWD_G_MAX_D;
-  return per_wave ? grid * WAVES_PER_BLOCK : grid;
+  return D > LN_BWD_G_MAX_D ? grid * WAVES_PER_BLOCK : grid;
 }
 
 // Adaptive split count (round 2): the fixed 64-way split left a D=1024
@@ -823,18 +881,33 @@ int ln_bwd_ws_rows(int D, int grid) {
 // profile); pick splits so stage 1 launches ~1024 blocks, then collapse
 // with a narrow second stage and a single-split final stage.  scratch
 // must hold COLSUM_MAX_SPLITS + COLSUM_MID rows (ops.cpp allocates it).
+//
+// One chain reduces several outputs at once: ws is [R, D] with D = n * unit
+// (n column slabs side by side).  The split count comes from `split_w`, not
+// from D, so a column is summed in the same order whether or not the caller
+// appended a further slab: asking for an extra output leaves the others
+// bit-identical.  out is [D] f32, or [D] bf16 when out_bf16 is set (the
+// final stage rounds on the way out).
 #define COLSUM_MAX_SPLITS 256
 #define COLSUM_MID 16
-hipError_t colsum_launch(const void* ws, void* scratch, void* out, int R,
-                         int D, hipStream_t stream) {
-  int gx = (D / 4 + 255) / 256;
-  dim3 grid1(gx, 1);
-  if (R <= COLSUM_MID) {
-    colsum_stage_kernel<<<grid1, 256, 0, stream>>>(
-        (const float*)ws, (float*)out, R, D, R);
-    return hipGetLastError();
+static hipError_t colsum_final(const float* in, void* out, int R, int D,
+                               int out_bf16, hipStream_t stream) {
+  dim3 grid1((D / 4 + 255) / 256, 1);
+  if (out_bf16) {
+    colsum_stage_bf16_kernel<<<grid1, 256, 0, stream>>>(in, (short*)out, R, D);
+  } else {
+    colsum_stage_kernel<<<grid1, 256, 0, stream>>>(in, (float*)out, R, D, R);
   }
-  int splits = 1024 / gx;
+  return hipGetLastError();
+}
+
+hipError_t colsum_launch(const void* ws, void* scratch, void* out, int R,
+                         int D, int split_w, int out_bf16,
+                         hipStream_t stream) {
+  int gx = (D / 4 + 255) / 256;
+  if (R <= COLSUM_MID)
+    return colsum_final((const float*)ws, out, R, D, out_bf16, stream);
+  int splits = 1024 / ((split_w / 4 + 255) / 256);
   if (splits > COLSUM_MAX_SPLITS) splits = COLSUM_MAX_SPLITS;
   if (splits > R) splits = R;
   int rows_per_split = (R + splits - 1) / splits;
@@ -842,20 +915,16 @@ hipError_t colsum_launch(const void* ws, void* scratch, void* out, int R,
       (const float*)ws, (float*)scratch, R, D, rows_per_split);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (splits <= COLSUM_MID) {
-    colsum_stage_kernel<<<grid1, 256, 0, stream>>>(
-        (const float*)scratch, (float*)out, splits, D, splits);
-    return hipGetLastError();
-  }
+  if (splits <= COLSUM_MID)
+    return colsum_final((const float*)scratch, out, splits, D, out_bf16,
+                        stream);
   float* mid = (float*)scratch + (long)COLSUM_MAX_SPLITS * D;
   int rps2 = (splits + COLSUM_MID - 1) / COLSUM_MID;
   colsum_stage_kernel<<<dim3(gx, COLSUM_MID), 256, 0, stream>>>(
       (const float*)scratch, mid, splits, D, rps2);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  colsum_stage_kernel<<<grid1, 256, 0, stream>>>(
-      mid, (float*)out, COLSUM_MID, D, COLSUM_MID);
-  return hipGetLastError();
+  return colsum_final(mid, out, COLSUM_MID, D, out_bf16, stream);
 }
 
 }  // extern "C"

@@ -15,10 +15,11 @@ hipError_t ln_fwd_launch(const void*, const void*, const void*, const void*,
                          void*, void*, void*, void*, int, int, float, int,
                          hipStream_t);
 hipError_t ln_bwd_launch(const void*, const void*, const void*, const void*,
-                         const void*, const void*, void*, void*, void*, int,
+                         const void*, const void*, void*, void*, int, int,
                          int, int, hipStream_t);
 int ln_bwd_ws_rows(int, int);
-hipError_t colsum_launch(const void*, void*, void*, int, int, hipStream_t);
+hipError_t colsum_launch(const void*, void*, void*, int, int, int, int,
+                         hipStream_t);
 hipError_t bias_gelu_fwd_launch(const void*, const void*, void*, long, int,
                                 int, hipStream_t);
 hipError_t bias_gelu_bwd_launch(const void*, const void*, const void*, void*,
@@ -60,11 +61,12 @@ hipError_t flash_fwd_packed_launch(const void*, const void*, const void*,
 hipError_t flash_bwd_fused_packed_launch(const void*, const void*,
                                          const void*, const void*,
                                          const void*, const void*, void*,
-                                         int, int, int, float, hipStream_t);
+                                         void*, int, int, int, float,
+                                         hipStream_t);
 hipError_t flash_dq_recompute_packed_launch(const void*, const void*,
                                             const void*, const void*,
                                             const void*, const void*, void*,
-                                            int, int, int, float,
+                                            void*, int, int, int, float,
                                             hipStream_t);
 hipError_t flash_dq_recompute_launch(const void*, const void*, const void*,
                                      const void*, const void*, const void*,
@@ -241,25 +243,37 @@ std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x,
   return {y, s_out, mean, rstd};
 }
 
+// Returns {dx, dgamma, dbeta} and, with want_dres, a fourth tensor dres_sum:
+// the column sum of the bf16 dx this call returns (the bias gradient of the
+// projection whose output was the LayerNorm's residual input).  The column
+// outputs are f32, or bf16 with out_bf16; they are slices of one [n * D]
+// tensor that a single colsum chain fills.
 std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
                                          torch::Tensor gamma, torch::Tensor mean,
                                          torch::Tensor rstd,
-                                         c10::optional<torch::Tensor> ds_extra) {
+                                         c10::optional<torch::Tensor> ds_extra,
+                                         bool want_dres, bool out_bf16) {
   check_bf16(dy, "dy"); check_bf16(x, "x"); check_bf16(gamma, "gamma");
   const int D = (int)x.size(-1);
   const long N = x.numel() / D;
   TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8, got ", D);
+  TORCH_CHECK(dy.numel() == x.numel(), "dy shape mismatch");
+  TORCH_CHECK(gamma.numel() == D, "gamma must be [D]");
+  check_f32(mean, "mean"); check_f32(rstd, "rstd");
+  TORCH_CHECK(mean.numel() == N && rstd.numel() == N,
+              "mean and rstd must be [N]");
   auto dx = torch::empty_like(x);
-  // bwd grid stays modest: the [rows, D] dgamma/dbeta workspace and its
+  // bwd grid stays modest: the [rows, n * D] partials workspace and its
   // column-sum scale linearly with the grid
   // (D > 4096 keeps one row per WAVE in global memory: a quarter of the grid)
   int grid = (int)std::min<long>((N + 3) / 4, D > 4096 ? 256 : 1024);
-  // one ws row per wave or per block, depending on the kernel the launcher
-  // picks for this D; either way the rows are reduced in fixed order
+  // one ws row per block (per wave on the wide path); either way the rows
+  // are reduced in fixed order
   long ws_rows = ln_bwd_ws_rows(D, grid);
+  const int n_out = want_dres ? 3 : 2;
+  const int W = n_out * D;
   auto opts = x.options().dtype(torch::kFloat32);
-  auto ws_dg = torch::empty({ws_rows, D}, opts);
-  auto ws_db = torch::empty({ws_rows, D}, opts);
+  auto ws = torch::empty({ws_rows, W}, opts);
   const void* de = nullptr;
   if (ds_extra.has_value()) {
     check_bf16(*ds_extra, "ds_extra");
@@ -268,16 +282,18 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
   }
   CHECK_HIP(ln_bwd_launch(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(),
                           mean.data_ptr(), rstd.data_ptr(), de, dx.data_ptr(),
-                          ws_dg.data_ptr(), ws_db.data_ptr(), (int)N, D, grid,
+                          ws.data_ptr(), n_out, (int)N, D, grid,
                           cur_stream()));
-  auto dgamma = torch::empty({D}, opts);
-  auto dbeta = torch::empty({D}, opts);
-  auto scratch = torch::empty({256 + 16, D}, opts);
-  CHECK_HIP(colsum_launch(ws_dg.data_ptr(), scratch.data_ptr(),
-                          dgamma.data_ptr(), (int)ws_rows, D, cur_stream()));
-  CHECK_HIP(colsum_launch(ws_db.data_ptr(), scratch.data_ptr(),
-                          dbeta.data_ptr(), (int)ws_rows, D, cur_stream()));
-  return {dx, dgamma, dbeta};
+  auto cols = torch::empty({W}, out_bf16 ? x.options() : opts);
+  auto scratch = torch::empty({256 + 16, W}, opts);
+  // splits from the two-slab width, with or without the third slab
+  CHECK_HIP(colsum_launch(ws.data_ptr(), scratch.data_ptr(), cols.data_ptr(),
+                          (int)ws_rows, W, 2 * D, out_bf16 ? 1 : 0,
+                          cur_stream()));
+  std::vector<torch::Tensor> out = {dx, cols.narrow(0, 0, D),
+                                    cols.narrow(0, D, D)};
+  if (want_dres) out.push_back(cols.narrow(0, 2 * D, D));
+  return out;
 }
 
 torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor b) {
@@ -296,8 +312,9 @@ torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor b) {
   return y;
 }
 
+// dbias is f32, or bf16 with out_bf16 (rounded by the final colsum stage).
 std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
-                                         torch::Tensor b) {
+                                         torch::Tensor b, bool out_bf16) {
   check_bf16(dy, "dy"); check_bf16(x, "x"); check_bf16(b, "b");
   const int D = (int)x.size(-1);
   const long n = x.numel();
@@ -313,11 +330,12 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
   CHECK_HIP(bias_gelu_bwd_launch(dy.data_ptr(), x.data_ptr(), b.data_ptr(),
                                  dx.data_ptr(), ws.data_ptr(), n, D, grid,
                                  cur_stream()));
-  auto dbias = torch::empty({D}, x.options().dtype(torch::kFloat32));
+  auto dbias = torch::empty(
+      {D}, out_bf16 ? x.options() : x.options().dtype(torch::kFloat32));
   auto scratch = torch::empty({256 + 16, D},
                              x.options().dtype(torch::kFloat32));
   CHECK_HIP(colsum_launch(ws.data_ptr(), scratch.data_ptr(), dbias.data_ptr(),
-                          grid, D, cur_stream()));
+                          grid, D, D, out_bf16 ? 1 : 0, cur_stream()));
   return {dx, dbias};
 }
 
@@ -625,12 +643,17 @@ std::vector<torch::Tensor> flash_fwd_packed(torch::Tensor qkv, long H,
   return {o, lse};
 }
 
-torch::Tensor flash_bwd_packed(torch::Tensor qkv, torch::Tensor o,
-                               torch::Tensor dout,
-                               c10::optional<torch::Tensor> mask,
-                               torch::Tensor lse, long H, double scale,
-                               c10::optional<torch::Tensor> seg) {
-  // full packed backward: ddot + dK/dV + dQ, all into one [B, L, 3D] grad
+namespace {
+
+// full packed backward: ddot + dK/dV + dQ, all into one [B, L, 3D] grad.
+// With want_bias also dqkv_bias [3D] bf16, the column sum of dqkv over all
+// B * L rows (the qkv projection's bias gradient): both kernels emit
+// per-workgroup column partials of what they store into one
+// [B * ceil(L / 128), 3D] f32 workspace and one colsum chain reduces it.
+std::vector<torch::Tensor> flash_bwd_packed_impl(
+    torch::Tensor qkv, torch::Tensor o, torch::Tensor dout,
+    c10::optional<torch::Tensor> mask, torch::Tensor lse, long H,
+    double scale, c10::optional<torch::Tensor> seg, bool want_bias) {
   const auto dims = check_flash_packed(qkv, H, {{"o", o}, {"dout", dout}},
                                        {{"lse", lse}});
   const long B = dims.B, L = dims.L;
@@ -641,15 +664,48 @@ torch::Tensor flash_bwd_packed(torch::Tensor qkv, torch::Tensor o,
                                  ddot.data_ptr(), (int)B, (int)H, (int)L,
                                  cur_stream()));
   auto dqkv = torch::empty_like(qkv);
+  const auto f32 = qkv.options().dtype(torch::kFloat32);
+  const long W = 3 * H * 64;
+  const long ws_rows = B * ((L + 127) / 128);
+  torch::Tensor ws;
+  void* ws_ptr = nullptr;
+  if (want_bias) {
+    ws = torch::empty({ws_rows, W}, f32);
+    ws_ptr = ws.data_ptr();
+  }
   CHECK_HIP(flash_bwd_fused_packed_launch(
       qkv.data_ptr(), dout.data_ptr(), mptr, sptr, lse.data_ptr(),
-      ddot.data_ptr(), dqkv.data_ptr(), (int)B, (int)H, (int)L, (float)scale,
-      cur_stream()));
+      ddot.data_ptr(), dqkv.data_ptr(), ws_ptr, (int)B, (int)H, (int)L,
+      (float)scale, cur_stream()));
   CHECK_HIP(flash_dq_recompute_packed_launch(
       qkv.data_ptr(), dout.data_ptr(), mptr, sptr, lse.data_ptr(),
-      ddot.data_ptr(), dqkv.data_ptr(), (int)B, (int)H, (int)L, (float)scale,
-      cur_stream()));
-  return dqkv;
+      ddot.data_ptr(), dqkv.data_ptr(), ws_ptr, (int)B, (int)H, (int)L,
+      (float)scale, cur_stream()));
+  if (!want_bias) return {dqkv};
+  auto dbias = torch::empty({W}, qkv.options());
+  auto scratch = torch::empty({256 + 16, W}, f32);
+  CHECK_HIP(colsum_launch(ws.data_ptr(), scratch.data_ptr(), dbias.data_ptr(),
+                          (int)ws_rows, (int)W, (int)W, 1, cur_stream()));
+  return {dqkv, dbias};
+}
+
+}  // namespace
+
+torch::Tensor flash_bwd_packed(torch::Tensor qkv, torch::Tensor o,
+                               torch::Tensor dout,
+                               c10::optional<torch::Tensor> mask,
+                               torch::Tensor lse, long H, double scale,
+                               c10::optional<torch::Tensor> seg) {
+  return flash_bwd_packed_impl(qkv, o, dout, mask, lse, H, scale, seg,
+                               false)[0];
+}
+
+// {dqkv, dqkv_bias}: see flash_bwd_packed_impl
+std::vector<torch::Tensor> flash_bwd_packed_bias(
+    torch::Tensor qkv, torch::Tensor o, torch::Tensor dout,
+    c10::optional<torch::Tensor> mask, torch::Tensor lse, long H,
+    double scale, c10::optional<torch::Tensor> seg) {
+  return flash_bwd_packed_impl(qkv, o, dout, mask, lse, H, scale, seg, true);
 }
 
 torch::Tensor flash_dq_recompute(torch::Tensor q, torch::Tensor k,
@@ -804,6 +860,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("mask"),
         py::arg("lse"), py::arg("H"), py::arg("scale"),
         py::arg("seg") = py::none());
+  m.def("flash_bwd_packed_bias", &flash_bwd_packed_bias,
+        "flash_bwd_packed plus the column sum of dqkv (qkv bias grad, bf16)",
+        py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("mask"),
+        py::arg("lse"), py::arg("H"), py::arg("scale"),
+        py::arg("seg") = py::none());
   m.def("fa_dot", &fa_dot, "rowsum(dO*O) per attention row");
   m.def("flash_dq", &flash_dq, "dQ = dS @ K (MFMA, tr_b16 K^T fragments)");
   m.def("bias_grad", &bias_grad, "bf16 column-sum for linear bias grads");
@@ -813,7 +874,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("out_repack", &out_repack, "attention output merge");
   m.def("out_repack_bwd", &out_repack_bwd, "attention output merge bwd");
   m.def("layernorm_fwd", &layernorm_fwd, "fused LayerNorm fwd (bf16, gfx950)");
-  m.def("layernorm_bwd", &layernorm_bwd, "fused LayerNorm bwd");
+  m.def("layernorm_bwd", &layernorm_bwd, "fused LayerNorm bwd",
+        py::arg("dy"), py::arg("x"), py::arg("gamma"), py::arg("mean"),
+        py::arg("rstd"), py::arg("ds_extra"), py::arg("want_dres") = false,
+        py::arg("out_bf16") = false);
   m.def("bias_gelu_fwd", &bias_gelu_fwd, "fused bias+GeLU fwd");
   m.def("lt_linear_gelu_bias", &lt_linear_gelu_bias,
         "hipBLASLt GEMM with fused GELU_BIAS epilogue (inference)");
@@ -821,7 +885,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "time the heuristic's top algos for a bf16 GEMM config");
   m.def("lt_probe_epilogue", &lt_probe_epilogue,
         "does this hipBLASLt have kernels for (m, n, k, epilogue)?");
-  m.def("bias_gelu_bwd", &bias_gelu_bwd, "fused bias+GeLU bwd");
+  m.def("bias_gelu_bwd", &bias_gelu_bwd, "fused bias+GeLU bwd",
+        py::arg("dy"), py::arg("x"), py::arg("b"),
+        py::arg("out_bf16") = false);
   m.def("softmax_fwd", &softmax_fwd, "fused scaled masked softmax fwd");
   m.def("softmax_bwd", &softmax_bwd, "fused softmax bwd");
   m.def("adamw_step", &adamw_step, "fused AdamW over flat params");

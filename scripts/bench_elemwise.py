@@ -71,6 +71,10 @@ def main():
            N * D * 2 * 3)
     report("ln_bwd+dsx", lambda: ext.layernorm_bwd(dy, x, g, mean, rstd, res),
            N * D * 2 * 4)
+    # the training path: bf16 column outputs plus the folded bias gradient
+    report("ln_bwd+dsx+dres",
+           lambda: ext.layernorm_bwd(dy, x, g, mean, rstd, res, True, True),
+           N * D * 2 * 4)
     del x, res, dy, out
 
     xf = torch.randn(N, Dff, device="cuda").to(torch.bfloat16)

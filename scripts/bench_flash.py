@@ -73,6 +73,35 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / iters
     print(f"r2 bwd chain (fused + dq_recompute) {dt*1e6:.1f} us")
+    del q, k, v, do, dq, dk, dv, o, lse, ddot
+
+    # the training path: packed [B, L, 3D] layout, whole backward binding,
+    # without and with the folded qkv bias gradient, and the reduction over
+    # dqkv that the fold replaces
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / iters
+
+    qkv = torch.randn(B, L, 3 * H * dh, device="cuda", dtype=torch.bfloat16)
+    dop = torch.randn(B, L, H * dh, device="cuda", dtype=torch.bfloat16)
+    o, lse = ext.flash_fwd_packed(qkv, H, mask, scale)
+    dt0 = timed(lambda: ext.flash_bwd_packed(qkv, o, dop, mask, lse, H,
+                                             scale))
+    print(f"flash_bwd_packed {dt0*1e6:.1f} us")
+    dqkv = ext.flash_bwd_packed(qkv, o, dop, mask, lse, H, scale)
+    dt2 = timed(lambda: dqkv.view(B * L, -1).sum(0))
+    print(f"dqkv.sum(0) (the reduce the fold replaces) {dt2*1e6:.1f} us")
+    if hasattr(ext, "flash_bwd_packed_bias"):
+        dt1 = timed(lambda: ext.flash_bwd_packed_bias(qkv, o, dop, mask, lse,
+                                                      H, scale))
+        print(f"flash_bwd_packed_bias {dt1*1e6:.1f} us  "
+              f"(+{(dt1-dt0)*1e6:.1f} us for the bias)")
 
 
 if __name__ == "__main__":

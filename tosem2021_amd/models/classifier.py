@@ -90,8 +90,9 @@ class FusedLayerNorm(nn.Module):
 # TunableOp table active: still a 13.5 ms/step REGRESSION (97.6 vs 84.1 ms
 # back-to-back on one box) — the explicit dgrad/wgrad matmul layouts are
 # not in the tuned table and dispatch worse than addmm's backward, exactly
-# as in round 1.  Default stays OFF; the ~1.4 ms of at::native::reduce
-# bias grads is the price of addmm's better GEMM dispatch.
+# as in round 1.  Default stays OFF; the at::native::reduce bias grads
+# that addmm's backward ran were since removed without touching the GEMM
+# calls (_FOLD_BIAS_GRAD below).
 _USE_FUSED_LINEAR = os.environ.get("TOSEM_FUSED_LINEAR", "0") == "1"
 # TOSEM_WGRAD=1: weight grads of the big projections through the custom
 # split-K MFMA wgrad kernel (csrc/wgrad_gemm.hip) + colsum bias grad;
@@ -99,7 +100,36 @@ _USE_FUSED_LINEAR = os.environ.get("TOSEM_FUSED_LINEAR", "0") == "1"
 _USE_WGRAD = os.environ.get("TOSEM_WGRAD", "0") == "1"
 
 
-def _linear(mod: nn.Linear, x: torch.Tensor) -> torch.Tensor:
+# Folded bias gradients (opt-in: TOSEM_FOLD_BIAS_GRAD=1, or the model's
+# fold_bias_grad keyword): attn.qkv (on the flash path), attn.proj and ffn.down
+# are called with their bias DETACHED — same addmm forward, same dgrad/wgrad
+# mm calls in backward, but autograd no longer runs sum(0) over the
+# [tokens, features] output gradient.  That gradient is exactly the dx the
+# next fused add+LayerNorm backward stores (proj, down) or the dqkv the
+# flash backward stores (qkv), and those kernels sum its columns while they
+# are in registers (residual_bias of ops.fused_add_layernorm, qkv_bias of
+# ops.flash_attention_packed).  This does not change how any GEMM is
+# called, unlike TOSEM_FUSED_LINEAR above.
+#
+# MEASURED, and why the default is OFF: 2.8 ms/step faster (81.4 -> 78.6 ms),
+# and after one step every gradient outside the three bias families is
+# bit-equal to the unrouted model's.  But the bias sums are taken in another
+# order, and AdamW normalises a gradient whatever its size: the k third of
+# qkv.bias has an analytic gradient of zero, so what it sees there is pure
+# rounding noise (~1e-7), and a reordered sum is DIFFERENT noise that moves
+# the parameter by about lr per step in another direction.  After 3 steps
+# those parameters are off by 80 % of their size, after 30 steps the loss
+# differs in the third digit (3.063 vs 3.077) — a different, equally valid
+# trajectory, not the same one.  With the routing off a 30-step run is
+# bit-identical to the one before these kernels existed (docs/PERF.md).
+_FOLD_BIAS_GRAD = os.environ.get("TOSEM_FOLD_BIAS_GRAD", "0") == "1"
+
+
+def _linear(mod: nn.Linear, x: torch.Tensor,
+            fold_bias: bool = False) -> torch.Tensor:
+    if fold_bias:
+        # the caller hands mod.bias to the LayerNorm that consumes the output
+        return F.linear(x, mod.weight, mod.bias.detach())
     if x.is_cuda and torch.is_grad_enabled():
         if _USE_WGRAD and ops.wgrad_linear_supported(
                 mod.out_features, mod.in_features,
@@ -126,18 +156,23 @@ class Attention(nn.Module):
         self.proj = nn.Linear(cfg.d_model, cfg.d_model, bias=True)
 
     def forward(self, x, mask_bias: Optional[torch.Tensor],
-                seg: Optional[torch.Tensor] = None):
+                seg: Optional[torch.Tensor] = None, fold_bias: bool = False):
         """seg: [B, L] int32 segment ids of a packed batch (exclusive with
-        mask_bias): attention stays inside each segment."""
+        mask_bias): attention stays inside each segment.  fold_bias: proj
+        runs with its bias detached; the caller routes proj.bias to the
+        LayerNorm that consumes the output (see _FOLD_BIAS_GRAD)."""
         B, L, D = x.shape
         if ops.flash_supported(self.head_dim, L):
             # MFMA flash kernels run straight on the packed [B, L, 3D]
             # projection output and write attention out (and, in backward,
             # every gradient) in the packed layouts — no repack kernels,
             # no [L, L] score tensor, O(L) attention memory
-            out = ops.flash_attention_packed(_linear(self.qkv, x), self.n_heads,
-                                             mask_bias, self.scale, seg)
-            return _linear(self.proj, out)
+            # (with fold_bias the flash backward also returns qkv.bias's
+            # gradient, the column sum of the dqkv it writes)
+            out = ops.flash_attention_packed(
+                _linear(self.qkv, x, fold_bias), self.n_heads, mask_bias,
+                self.scale, seg, self.qkv.bias if fold_bias else None)
+            return _linear(self.proj, out, fold_bias)
         if seg is not None:
             if x.is_cuda:
                 # no O(L^2) fallback: packing exists to cut attention work
@@ -151,14 +186,14 @@ class Attention(nn.Module):
             s = torch.matmul(q, k.transpose(-1, -2)).float() * self.scale
             p = torch.softmax(s + ops.reference.segment_bias(seg), dim=-1)
             out = torch.matmul(p.to(v.dtype), v)
-            return self.proj(ops.out_repack(out))
+            return _linear(self.proj, ops.out_repack(out), fold_bias)
         # general-shape fallback: gather kernel to bmm-ready
         # [3, B, H, L, dh] (csrc/repack.hip), bmm + fused softmax
         q, k, v = ops.qkv_repack(self.qkv(x), self.n_heads)  # [B, H, L, dh]
         scores = torch.matmul(q, k.transpose(-1, -2))  # [B, H, L, L]
         p = ops.fused_softmax(scores, mask_bias, self.scale)
         out = torch.matmul(p, v)                       # [B, H, L, dh]
-        return self.proj(ops.out_repack(out))
+        return _linear(self.proj, ops.out_repack(out), fold_bias)
 
 
 class FFN(nn.Module):
@@ -170,7 +205,7 @@ class FFN(nn.Module):
         self.up_bias = nn.Parameter(torch.zeros(cfg.d_ff))
         self.down = nn.Linear(cfg.d_ff, cfg.d_model, bias=True)
 
-    def forward(self, x):
+    def forward(self, x, fold_bias: bool = False):
         if x.is_cuda and not torch.is_grad_enabled():
             # inference: bias+GeLU fused into the up GEMM's epilogue
             B, L, D = x.shape
@@ -179,7 +214,7 @@ class FFN(nn.Module):
             return self.down(a.view(B, L, -1))
         h = _linear(self.up, x)
         h = ops.fused_bias_gelu(h, self.up_bias)
-        return _linear(self.down, h)
+        return _linear(self.down, h, fold_bias)
 
 
 class EncoderBlock(nn.Module):
@@ -189,6 +224,12 @@ class EncoderBlock(nn.Module):
     (ops.fused_add_layernorm), so the block never launches a separate
     elementwise add: it receives the previous sublayer's (x, delta), and
     returns its own.
+
+    With fold_bias the bias gradient of the projection behind each delta is
+    computed by the LayerNorm backward that consumes the delta: proj.bias
+    goes to this block's ln2; the caller passes the previous block's
+    ffn.down.bias in as delta_bias and hands this block's on to the next
+    consumer of the returned delta (the next block's ln1, or ln_f).
     """
 
     def __init__(self, cfg: MLTCConfig):
@@ -202,25 +243,40 @@ class EncoderBlock(nn.Module):
     def _drop(self, h):
         return F.dropout(h, self.dropout, self.training) if self.dropout else h
 
-    def forward(self, x, delta, mask_bias, seg=None):
+    def fold_ok(self) -> bool:
+        """The delta's gradient is the LayerNorm's dx only when no dropout
+        sits between the projection and the add."""
+        return not (self.dropout and self.training)
+
+    def forward(self, x, delta, mask_bias, seg=None, delta_bias=None,
+                fold_bias: bool = False):
         if delta is None:
             y1 = ops.fused_layernorm(x, self.ln1.weight, self.ln1.bias,
                                      self.ln1.eps)
             s1 = x
         else:
             y1, s1 = ops.fused_add_layernorm(x, delta, self.ln1.weight,
-                                             self.ln1.bias, self.ln1.eps)
-        h = self._drop(self.attn(y1, mask_bias, seg))
-        y2, s2 = ops.fused_add_layernorm(s1, h, self.ln2.weight,
-                                         self.ln2.bias, self.ln2.eps)
-        h2 = self._drop(self.ffn(y2))
+                                             self.ln1.bias, self.ln1.eps,
+                                             delta_bias)
+        fold_bias = fold_bias and self.fold_ok()
+        h = self._drop(self.attn(y1, mask_bias, seg, fold_bias))
+        y2, s2 = ops.fused_add_layernorm(
+            s1, h, self.ln2.weight, self.ln2.bias, self.ln2.eps,
+            self.attn.proj.bias if fold_bias else None)
+        h2 = self._drop(self.ffn(y2, fold_bias))
         return s2, h2
 
 
 class MLTC(nn.Module):
-    def __init__(self, cfg: MLTCConfig):
+    def __init__(self, cfg: MLTCConfig,
+                 fold_bias_grad: Optional[bool] = None):
+        """fold_bias_grad: None = on for GPU inputs if
+        TOSEM_FOLD_BIAS_GRAD=1 (default off); True = on, also on the CPU
+        reference path (for tests); False = off.  Whatever the setting, the fold is taken only
+        where it is exact: see _fold_active."""
         super().__init__()
         self.cfg = cfg
+        self.fold_bias_grad = fold_bias_grad
         self.tok_emb = nn.Embedding(cfg.vocab_size, cfg.d_model)
         self.pos_emb = nn.Embedding(cfg.max_seq, cfg.d_model)
         self.blocks = nn.ModuleList(EncoderBlock(cfg) for _ in range(cfg.n_layers))
@@ -236,6 +292,32 @@ class MLTC(nn.Module):
             nn.init.normal_(m.weight, std=0.02)
             if isinstance(m, nn.Linear) and m.bias is not None:
                 nn.init.zeros_(m.bias)
+
+    def _fold_active(self, x: torch.Tensor) -> bool:
+        """Whether proj/down bias gradients are folded into the LayerNorm
+        backward for this call: grad enabled, no active dropout, neither of
+        the Linear-replacing A/B knobs set, and switched on."""
+        if self.fold_bias_grad is None:
+            on = _FOLD_BIAS_GRAD and x.is_cuda
+        else:
+            on = self.fold_bias_grad
+        return (on and torch.is_grad_enabled()
+                and not (self.cfg.dropout and self.training)
+                and not _USE_FUSED_LINEAR and not _USE_WGRAD)
+
+    def _run_blocks(self, x, mask_bias, seg):
+        fold = self._fold_active(x)
+        delta = delta_bias = None
+        for blk in self.blocks:
+            x, delta = blk(x, delta, mask_bias, seg, delta_bias, fold)
+            # the bias that belongs to this delta travels on with it
+            delta_bias = blk.ffn.down.bias if fold and blk.fold_ok() else None
+        if delta is None:
+            return self.ln_f(x)
+        x, _ = ops.fused_add_layernorm(x, delta, self.ln_f.weight,
+                                       self.ln_f.bias, self.ln_f.eps,
+                                       delta_bias)
+        return x
 
     def forward(self, tokens: Optional[torch.Tensor],
                 attn_mask: Optional[torch.Tensor] = None,
@@ -257,14 +339,7 @@ class MLTC(nn.Module):
             mask_bias = torch.where(
                 attn_mask, 0.0, -1e9
             ).to(torch.float32).contiguous()
-        delta = None
-        for blk in self.blocks:
-            x, delta = blk(x, delta, mask_bias)
-        if delta is None:
-            x = self.ln_f(x)
-        else:
-            x, _ = ops.fused_add_layernorm(x, delta, self.ln_f.weight,
-                                           self.ln_f.bias, self.ln_f.eps)
+        x = self._run_blocks(x, mask_bias, None)
         # masked mean-pool over valid tokens (fused kernel: csrc/pool.hip)
         pooled = ops.masked_mean_pool(x, attn_mask)
         return {name: head(pooled) for name, head in self.heads.items()}
@@ -277,14 +352,7 @@ class MLTC(nn.Module):
             tokens = packing.tokens
         R, L = tokens.shape
         x = self.tok_emb(tokens) + self.pos_emb(packing.pos)
-        delta = None
-        for blk in self.blocks:
-            x, delta = blk(x, delta, None, packing.seg)
-        if delta is None:
-            x = self.ln_f(x)
-        else:
-            x, _ = ops.fused_add_layernorm(x, delta, self.ln_f.weight,
-                                           self.ln_f.bias, self.ln_f.eps)
+        x = self._run_blocks(x, None, packing.seg)
         # per-example mean-pool over the flattened positions
         pooled = ops.segment_mean_pool(x.reshape(R * L, -1), packing.seg_start,
                                        packing.seg_len, packing.pos2seg)
@@ -337,7 +405,8 @@ class MLTC(nn.Module):
         return total
 
 
-def build_model(name_or_cfg, dtype=torch.bfloat16) -> MLTC:
+def build_model(name_or_cfg, dtype=torch.bfloat16,
+                fold_bias_grad: Optional[bool] = None) -> MLTC:
     cfg = CONFIGS[name_or_cfg] if isinstance(name_or_cfg, str) else name_or_cfg
-    model = MLTC(cfg)
+    model = MLTC(cfg, fold_bias_grad)
     return model.to(dtype)

@@ -59,10 +59,11 @@ class _LayerNormFn(torch.autograd.Function):
         x, gamma, mean, rstd = ctx.saved_tensors
         dy = dy.contiguous()
         if x.is_cuda:
-            dx, dgamma, dbeta = hip_ops().layernorm_bwd(dy, x, gamma, mean,
-                                                        rstd, None)
-        else:
-            dx, dgamma, dbeta = reference.layernorm_bwd(dy, x, gamma, mean, rstd)
+            # the final colsum stage writes bf16: no convert launches
+            dx, dgamma, dbeta = hip_ops().layernorm_bwd(
+                dy, x, gamma, mean, rstd, None, False, True)
+            return dx, dgamma, dbeta, None
+        dx, dgamma, dbeta = reference.layernorm_bwd(dy, x, gamma, mean, rstd)
         return dx, dgamma.to(gamma.dtype), dbeta.to(gamma.dtype), None
 
 
@@ -72,10 +73,17 @@ def fused_layernorm(x, gamma, beta, eps: float = 1e-5):
 
 class _AddLayerNormFn(torch.autograd.Function):
     """(y, s) = (LN(x + residual), x + residual) — the residual-stream add is
-    fused into the LN kernel's first read (one kernel, no separate add)."""
+    fused into the LN kernel's first read (one kernel, no separate add).
+
+    residual_bias (optional) is the bias of the projection that produced
+    `residual`, called with that bias detached.  It takes no part in the
+    forward; its gradient is the column sum of the dx this backward returns
+    for `residual`, which the LN backward kernel emits next to dgamma/dbeta,
+    so the projection's backward need not re-read dx to reduce it."""
 
     @staticmethod
-    def forward(ctx, x, residual, gamma, beta, eps):
+    def forward(ctx, x, residual, gamma, beta, eps, residual_bias=None):
+        ctx.rb_dtype = None if residual_bias is None else residual_bias.dtype
         if x.is_cuda:
             y, s, mean, rstd = hip_ops().layernorm_fwd(x, residual, gamma,
                                                        beta, eps)
@@ -89,22 +97,34 @@ class _AddLayerNormFn(torch.autograd.Function):
     def backward(ctx, dy, ds):
         s, gamma, mean, rstd = ctx.saved_tensors
         dy = dy.contiguous()
+        want_dres = ctx.rb_dtype is not None and ctx.needs_input_grad[5]
+        dres = None
         if s.is_cuda:
             # the downstream residual grad ds is added INSIDE the kernel
             de = ds.contiguous() if ds is not None else None
-            dx, dgamma, dbeta = hip_ops().layernorm_bwd(dy, s, gamma, mean,
-                                                        rstd, de)
-        else:
-            dx, dgamma, dbeta = reference.layernorm_bwd(dy, s, gamma, mean, rstd)
-            if ds is not None:
-                dx = dx + ds
-        return dx, dx, dgamma.to(gamma.dtype), dbeta.to(gamma.dtype), None
+            out = hip_ops().layernorm_bwd(dy, s, gamma, mean, rstd, de,
+                                          want_dres, True)
+            dx, dgamma, dbeta = out[:3]
+            if want_dres:
+                dres = out[3].to(ctx.rb_dtype)  # no-op for a bf16 bias
+            return dx, dx, dgamma, dbeta, None, dres
+        dx, dgamma, dbeta = reference.layernorm_bwd(dy, s, gamma, mean, rstd)
+        if ds is not None:
+            dx = dx + ds
+        if want_dres:
+            dres = reference.folded_bias_grad(dx).to(ctx.rb_dtype)
+        return (dx, dx, dgamma.to(gamma.dtype), dbeta.to(gamma.dtype), None,
+                dres)
 
 
-def fused_add_layernorm(x, residual, gamma, beta, eps: float = 1e-5):
-    """Returns (y, s): y = LN(x+residual), s = the new residual stream."""
+def fused_add_layernorm(x, residual, gamma, beta, eps: float = 1e-5,
+                        residual_bias=None):
+    """Returns (y, s): y = LN(x+residual), s = the new residual stream.
+
+    residual_bias: see _AddLayerNormFn — the detached-in-forward bias of the
+    projection behind `residual`, which receives its gradient from here."""
     return _AddLayerNormFn.apply(x.contiguous(), residual.contiguous(),
-                                 gamma, beta, eps)
+                                 gamma, beta, eps, residual_bias)
 
 
 class _BiasGeluFn(torch.autograd.Function):
@@ -120,9 +140,9 @@ class _BiasGeluFn(torch.autograd.Function):
         x, b = ctx.saved_tensors
         dy = dy.contiguous()
         if x.is_cuda:
-            dx, dbias = hip_ops().bias_gelu_bwd(dy, x, b)
-        else:
-            dx, dbias = reference.bias_gelu_bwd(dy, x, b)
+            # the final colsum stage writes bf16: no convert launch
+            return tuple(hip_ops().bias_gelu_bwd(dy, x, b, True))
+        dx, dbias = reference.bias_gelu_bwd(dy, x, b)
         return dx, dbias.to(b.dtype)
 
 
@@ -378,10 +398,17 @@ class _FlashAttentionPackedFn(torch.autograd.Function):
     [B, L, 3D] -> attention output [B, L, D] (round 2).  The strided-
     geometry kernels read q/k/v from and write every gradient back into
     the packed layouts, eliminating the qkv_repack / out_repack kernel
-    quartet (fwd gather, bwd3 merge, out fwd/bwd) from the step."""
+    quartet (fwd gather, bwd3 merge, out fwd/bwd) from the step.
+
+    qkv_bias (optional) is the bias of the projection that produced qkv,
+    called with that bias detached.  It takes no part in the forward; its
+    gradient is the column sum of dqkv, which the backward kernels emit as
+    per-workgroup partials while the tiles are in registers, so the
+    projection's backward need not re-read dqkv to reduce it."""
 
     @staticmethod
-    def forward(ctx, qkv, n_heads, mask, scale, seg=None):
+    def forward(ctx, qkv, n_heads, mask, scale, seg=None, qkv_bias=None):
+        ctx.qb_dtype = None if qkv_bias is None else qkv_bias.dtype
         if qkv.is_cuda:
             o, lse = hip_ops().flash_fwd_packed(qkv, n_heads, mask, scale,
                                                 seg)
@@ -407,10 +434,16 @@ class _FlashAttentionPackedFn(torch.autograd.Function):
         n_heads, mask, scale = ctx.n_heads, ctx.mask, ctx.scale
         seg = ctx.seg
         do = do.contiguous()
+        want_bias = ctx.qb_dtype is not None and ctx.needs_input_grad[5]
         if qkv.is_cuda:
+            if want_bias:
+                dqkv, dbias = hip_ops().flash_bwd_packed_bias(
+                    qkv, o, do, mask, lse, n_heads, scale, seg)
+                # no-op for a bf16 bias
+                return dqkv, None, None, None, None, dbias.to(ctx.qb_dtype)
             dqkv = hip_ops().flash_bwd_packed(qkv, o, do, mask, lse,
                                               n_heads, scale, seg)
-            return dqkv, None, None, None, None
+            return dqkv, None, None, None, None, None
         bias = reference.segment_bias(seg) if seg is not None else None
         B, L, D3 = qkv.shape
         d = D3 // 3
@@ -427,13 +460,18 @@ class _FlashAttentionPackedFn(torch.autograd.Function):
         dqkv = torch.cat(
             [t.transpose(1, 2).reshape(B, L, d) for t in (dq, dk, dv)],
             dim=-1)
-        return dqkv, None, None, None, None
+        dbias = None
+        if want_bias:
+            dbias = reference.folded_bias_grad(dqkv).to(ctx.qb_dtype)
+        return dqkv, None, None, None, None, dbias
 
 
 def flash_attention_packed(qkv, n_heads: int, mask=None, scale: float = 1.0,
-                           seg=None):
+                           seg=None, qkv_bias=None):
     """qkv: [B, L, 3*n_heads*64] bf16 (the fused projection output);
     returns [B, L, n_heads*64] ready for the output projection.
+    qkv_bias: see _FlashAttentionPackedFn — the detached-in-forward bias of
+    the qkv projection, which receives its gradient from here.
 
     mask: optional [B, L] f32 additive key bias; a bias <= -1e8 is treated
     as fully masked (its probability is exactly 0 and wholly masked tiles
@@ -444,7 +482,7 @@ def flash_attention_packed(qkv, n_heads: int, mask=None, scale: float = 1.0,
     verifies it on the host), not checked on the device."""
     _check_mask_seg(mask, seg)
     return _FlashAttentionPackedFn.apply(qkv.contiguous(), n_heads, mask,
-                                         scale, seg)
+                                         scale, seg, qkv_bias)
 
 
 def flash_supported(head_dim: int, L: int) -> bool:

@@ -54,6 +54,13 @@ def layernorm_bwd(
     return dx.reshape(x.shape).to(x.dtype), dgamma, dbeta
 
 
+def folded_bias_grad(g: torch.Tensor) -> torch.Tensor:
+    """Bias gradient of a projection whose output gradient is g: the f32 sum
+    of g over every dim but the last — what addmm's backward computes with
+    sum(0), and what the HIP kernels that produce g emit alongside it."""
+    return g.float().reshape(-1, g.shape[-1]).sum(dim=0)
+
+
 def bias_gelu_fwd(x: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     pre = x.float() + b.float()
     return torch.nn.functional.gelu(pre, approximate="tanh").to(x.dtype)
