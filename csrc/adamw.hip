@@ -15,8 +15,17 @@
 //    every buffer untouched when the gradient was not finite.
 
 #include "common.h"
+#include "launchers.h"
 
 #define AD_BLOCK 256
+
+// Launch geometry of both entry points: one thread per 4-wide group,
+// grid-stride past the cap.
+#define AD_MAX_GRID 2048
+static int adamw_grid(long n) {
+  long blocks = (n / 4 + AD_BLOCK - 1) / AD_BLOCK;
+  return (int)(blocks < AD_MAX_GRID ? blocks : AD_MAX_GRID);
+}
 
 // One 4-wide group: updates mm, vv, mw in place, returns the bf16 weights.
 //
@@ -110,7 +119,8 @@ adamw_clipped_kernel(short* __restrict__ p_bf16,
 extern "C" hipError_t adamw_launch(void* p_bf16, const void* grad, int grad_is_f32,
                         void* m, void* v, void* master, long n, float lr,
                         float beta1, float beta2, float eps, float wd,
-                        int step, float grad_scale, int grid, hipStream_t s) {
+                        int step, float grad_scale, hipStream_t s) {
+  const int grid = adamw_grid(n);
   float bc1 = 1.0f / (1.0f - powf(beta1, (float)step));
   float bc2 = 1.0f / (1.0f - powf(beta2, (float)step));
   if (grad_is_f32)
@@ -127,7 +137,8 @@ extern "C" hipError_t adamw_launch(void* p_bf16, const void* grad, int grad_is_f
 extern "C" hipError_t adamw_clipped_launch(
     void* p_bf16, const void* grad, int grad_is_f32, void* m, void* v,
     void* master, long n, float lr, float beta1, float beta2, float eps,
-    float wd, int step, const void* clip_state, int grid, hipStream_t s) {
+    float wd, int step, const void* clip_state, hipStream_t s) {
+  const int grid = adamw_grid(n);
   float bc1 = 1.0f / (1.0f - powf(beta1, (float)step));
   float bc2 = 1.0f / (1.0f - powf(beta2, (float)step));
   if (grad_is_f32)

@@ -2,7 +2,7 @@
 //
 // y = gelu(x + b); bwd recomputes the pre-activation from x,b (no saved
 // activation: 1 extra read instead of a [N,Dff] bf16 save — HBM3E-friendly).
-// dbias uses deterministic per-block LDS partials + colsum (layernorm.hip).
+// dbias uses deterministic per-block LDS partials + colsum (colsum.hip).
 // x: [N, D] bf16 row-major, b: [D] bf16.
 //
 // Round 2: 4 packets per thread per iteration for memory-level parallelism,
@@ -12,9 +12,12 @@
 // stride), which broke per-instruction coalescing and measured ~15% slower
 // than round 1.  Fast path needs the grid stride and the per-packet stride
 // (BG_BLOCK*8 = 2048) multiples of D and n % 8 == 0; generic fallback
-// otherwise (host rounds the grid accordingly).
+// otherwise (bias_gelu_grid below rounds the grid accordingly).
 
 #include "common.h"
+#include "launchers.h"
+#include <algorithm>
+#include <numeric>
 
 #define BG_BLOCK 256
 #define BG_PK 4                      // packets of 8 bf16 per iteration
@@ -190,10 +193,29 @@ bias_gelu_bwd_kernel(const short* __restrict__ dy, const short* __restrict__ x,
   for (int i = threadIdx.x; i < D; i += BG_BLOCK) out[i] = sdb[i];
 }
 
+// Launch geometry, shared by forward and backward: one block per
+// BG_BLOCK * BG_PK packets up to `cap`, then rounded UP to a multiple of
+// D / gcd(D, BG_TILE * BG_PK) so that the kernels' grid stride
+// (grid * BG_TILE * BG_PK elements) is a multiple of D: their fast path, with
+// a fixed per-thread column window.  A D whose rounding unit exceeds
+// BG_MAX_ROUND_UNIT keeps the unrounded grid and takes the generic path.
+// The backward cap is lower because its [grid, D] dbias workspace and the
+// column sum over it scale with the grid.
+#define BG_FWD_MAX_GRID 4096
+#define BG_BWD_MAX_GRID 1024
+#define BG_MAX_ROUND_UNIT 2048
+static int bias_gelu_grid(long n_elem, int D, long cap) {
+  long grid = std::min((n_elem / (BG_PK * 8) + BG_BLOCK - 1) / BG_BLOCK, cap);
+  const long unit = D / std::gcd((long)D, (long)(BG_TILE * BG_PK));
+  if (unit <= BG_MAX_ROUND_UNIT) grid = (grid + unit - 1) / unit * unit;
+  return (int)grid;
+}
+
 extern "C" {
 
 hipError_t bias_gelu_fwd_launch(const void* x, const void* b, void* y,
-                                long n_elem, int D, int grid, hipStream_t s) {
+                                long n_elem, int D, hipStream_t s) {
+  const int grid = bias_gelu_grid(n_elem, D, BG_FWD_MAX_GRID);
   bias_gelu_fwd_kernel<<<grid, BG_BLOCK, 0, s>>>((const short*)x, (const short*)b,
                                                  (short*)y, n_elem, D);
   return hipGetLastError();
@@ -201,7 +223,8 @@ hipError_t bias_gelu_fwd_launch(const void* x, const void* b, void* y,
 
 hipError_t bias_gelu_bwd_launch(const void* dy, const void* x, const void* b,
                                 void* dx, void* ws_dbias, long n_elem, int D,
-                                int grid, hipStream_t s) {
+                                hipStream_t s) {
+  const int grid = bias_gelu_grid(n_elem, D, BG_BWD_MAX_GRID);
   // [D] block partial, or the [BG_PK * BG_TILE] merge slab of the !OWNED
   // fast path, whichever the kernel will use
   size_t shm = (size_t)D * sizeof(float);
@@ -217,6 +240,11 @@ hipError_t bias_gelu_bwd_launch(const void* dy, const void* x, const void* b,
         (float*)ws_dbias, n_elem, D);
   }
   return hipGetLastError();
+}
+
+// One ws_dbias row per block of the backward grid.
+int bias_gelu_bwd_ws_rows(long n_elem, int D) {
+  return bias_gelu_grid(n_elem, D, BG_BWD_MAX_GRID);
 }
 
 }  // extern "C"

@@ -76,8 +76,9 @@ __device__ __forceinline__ float gelu_tanh_grad(float x) {
   return 0.5f * (1.0f + t) + 0.5f * x * sech2 * k0 * (1.0f + 3.0f * k1 * x2);
 }
 
-// Kernel files expose C-linkage launchers returning hipError_t; the torch
-// binding layer (ops.cpp) is the only place that includes torch headers.
+// Kernel files expose C-linkage launchers returning hipError_t, all declared
+// in launchers.h; the torch binding layer (ops.cpp) is the only place that
+// includes torch headers.
 
 // Place `group` consecutive block ids on the same XCD (dispatcher maps block
 // b -> XCD b % 8; guide T1).  Bijective when (n_blocks / group) % 8 == 0;

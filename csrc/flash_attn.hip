@@ -25,6 +25,7 @@
 //    32-row kv block, so a workgroup covers 128 kv rows.
 
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(2))) unsigned uint2_t;
@@ -565,8 +566,17 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
 }
 
 // Grid of a kernel whose workgroup owns `rows_per_wg` rows of one (b, h).
+static int fa_row_blocks(int B, int L, int rows_per_wg) {
+  return B * ((L + rows_per_wg - 1) / rows_per_wg);
+}
 static dim3 fa_grid(int B, int H, int L, int rows_per_wg) {
-  return dim3(B * H * ((L + rows_per_wg - 1) / rows_per_wg));
+  return dim3(H * fa_row_blocks(B, L, rows_per_wg));
+}
+
+// Rows of the packed backward's bias_ws: one per FA_QWG-row block of a batch
+// element, i.e. the fused backward's grid over one head.
+extern "C" int flash_bias_ws_rows(int B, int L) {
+  return fa_row_blocks(B, L, FA_QWG);
 }
 
 // Every launcher below takes an optional seg (int32 [B, L], nullptr = none)
@@ -922,8 +932,8 @@ extern "C" hipError_t flash_bwd_fused_launch(
 }
 
 // packed: qkv/dqkv [B, L, 3D], dout [B, L, D]; dk/dv land inside dqkv.
-// bias_ws (optional): [B * ceil(L / 128), 3D] f32 column partials, the k and
-// v thirds are written here.
+// bias_ws (optional): [flash_bias_ws_rows(B, L), 3D] f32 column partials, the
+// k and v thirds are written here.
 extern "C" hipError_t flash_bwd_fused_packed_launch(
     const void* qkv, const void* dout, const void* mask, const void* seg,
     const void* lse, const void* ddot, void* dqkv, void* bias_ws, int B,

@@ -20,6 +20,7 @@
 // Read-only pass: 2 B/elem (bf16) against the AdamW kernel's 48 B/elem.
 
 #include "common.h"
+#include "launchers.h"
 
 #define GN_BLOCK 256
 #define GN_WAVES (GN_BLOCK / WAVE)

@@ -13,6 +13,8 @@
 #include <c10/hip/HIPStream.h>
 #include <hipblaslt/hipblaslt.h>
 
+#include "lt_gemm.h"
+
 #include <chrono>
 #include <map>
 #include <mutex>

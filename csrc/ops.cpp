@@ -1,98 +1,17 @@
 // Torch bindings for the tosem2021_amd gfx950 HIP kernels.
 //
 // Host-only translation unit: device code lives in the *.hip files, exposed
-// through C-linkage launchers.  Uses the HIP-native ATen stream API directly
-// (c10::hip) — no CUDA names, no hipify translation of this file is needed.
+// through C-linkage launchers declared once in launchers.h.  A kernel file
+// owns its launch geometry and workspace sizes; this file asks for them.
+// Uses the HIP-native ATen stream API directly (c10::hip) — no CUDA names, no
+// hipify translation of this file is needed.
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <numeric>
 
-extern "C" {
-hipError_t ln_fwd_launch(const void*, const void*, const void*, const void*,
-                         void*, void*, void*, void*, int, int, float, int,
-                         hipStream_t);
-hipError_t ln_bwd_launch(const void*, const void*, const void*, const void*,
-                         const void*, const void*, void*, void*, int, int,
-                         int, int, hipStream_t);
-int ln_bwd_ws_rows(int, int);
-hipError_t colsum_launch(const void*, void*, void*, int, int, int, int,
-                         hipStream_t);
-hipError_t bias_gelu_fwd_launch(const void*, const void*, void*, long, int,
-                                int, hipStream_t);
-hipError_t bias_gelu_bwd_launch(const void*, const void*, const void*, void*,
-                                void*, long, int, int, hipStream_t);
-hipError_t softmax_fwd_launch(const void*, const void*, void*, long, int, int,
-                              float, int, hipStream_t);
-hipError_t softmax_bwd_launch(const void*, const void*, void*, long, int,
-                              float, int, hipStream_t);
-hipError_t adamw_launch(void*, const void*, int, void*, void*, void*, long,
-                        float, float, float, float, float, int, float, int,
-                        hipStream_t);
-hipError_t adamw_clipped_launch(void*, const void*, int, void*, void*, void*,
-                                long, float, float, float, float, float, int,
-                                const void*, int, hipStream_t);
-int grad_norm_grid(long);
-hipError_t grad_clip_state_launch(const void*, int, long, float, float, void*,
-                                  void*, hipStream_t);
-hipError_t qkv_repack_launch(const void*, void*, int, int, int, int, int,
-                             hipStream_t);
-hipError_t out_repack_launch(const void*, void*, int, int, int, int, int,
-                             hipStream_t);
-hipError_t qkv_repack_bwd3_launch(const void*, const void*, const void*,
-                                  void*, int, int, int, int, hipStream_t);
-hipError_t flash_fwd_launch(const void*, const void*, const void*, const void*,
-                            const void*, void*, void*, int, int, int, float,
-                            hipStream_t);
-hipError_t p_from_lse_launch(const void*, const void*, const void*, void*,
-                             long, int, int, float, int, hipStream_t);
-hipError_t flash_bwd_fused_launch(const void*, const void*, const void*,
-                                  const void*, const void*, const void*,
-                                  const void*, const void*, void*, void*,
-                                  void*, int, int, int, float, hipStream_t);
-hipError_t fa_dot_launch(const void*, const void*, void*, long, hipStream_t);
-hipError_t fa_dot_packed_launch(const void*, const void*, void*, int, int,
-                                int, hipStream_t);
-hipError_t flash_fwd_packed_launch(const void*, const void*, const void*,
-                                   void*, void*, int, int, int, float,
-                                   hipStream_t);
-hipError_t flash_bwd_fused_packed_launch(const void*, const void*,
-                                         const void*, const void*,
-                                         const void*, const void*, void*,
-                                         void*, int, int, int, float,
-                                         hipStream_t);
-hipError_t flash_dq_recompute_packed_launch(const void*, const void*,
-                                            const void*, const void*,
-                                            const void*, const void*, void*,
-                                            void*, int, int, int, float,
-                                            hipStream_t);
-hipError_t flash_dq_recompute_launch(const void*, const void*, const void*,
-                                     const void*, const void*, const void*,
-                                     const void*, const void*, void*, int,
-                                     int, int, float, hipStream_t);
-hipError_t flash_dq_launch(const void*, const void*, void*, int, int, int,
-                           hipStream_t);
-hipError_t masked_pool_fwd_launch(const void*, const void*, void*, void*,
-                                  void*, int, int, int, hipStream_t);
-hipError_t masked_pool_bwd_launch(const void*, const void*, const void*,
-                                  void*, int, int, int, hipStream_t);
-hipError_t segment_pool_fwd_launch(const void*, const void*, const void*,
-                                   void*, int, long, int, hipStream_t);
-hipError_t segment_pool_bwd_launch(const void*, const void*, const void*,
-                                   void*, int, long, int, hipStream_t);
-hipError_t tr_probe_launch(const void*, void*, int, hipStream_t);
-hipError_t colsum_bf16_launch(const void*, void*, void*, long, int,
-                              hipStream_t);
-hipError_t wgrad_gemm_launch(const void*, const void*, void*, void*, int,
-                             int, long, int, hipStream_t);
-}
-
-torch::Tensor lt_linear_gelu_bias(torch::Tensor, torch::Tensor,
-                                  torch::Tensor);
-bool lt_probe_epilogue(long, long, long, long);
-std::vector<double> lt_bench_algos(long, long, long, bool, bool, long);
+#include "launchers.h"
+#include "lt_gemm.h"
 
 namespace {
 
@@ -116,6 +35,63 @@ void check_f32(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
   TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must be f32");
   TORCH_CHECK(t.device().is_cuda(), name, " must be on GPU");
+}
+
+// `t` is exactly `want`; `shape` is how the message spells it, e.g. "[B, L]".
+void check_shape(const torch::Tensor& t, const char* name,
+                 at::IntArrayRef want, const char* shape) {
+  TORCH_CHECK(t.sizes() == want, name, " must be ", shape);
+}
+
+// `t` holds exactly `n` elements, whatever its rank.
+void check_numel(const torch::Tensor& t, const char* name, long n,
+                 const char* shape) {
+  TORCH_CHECK(t.numel() == n, name, " must be ", shape);
+}
+
+void check_mult8(long v, const char* name) {
+  TORCH_CHECK(v % 8 == 0, name, " must be a multiple of 8, got ", v);
+}
+
+// Optional additive softmax key mask: f32, contiguous, on the GPU, exactly
+// [B, Lk] for 4-D scores [B, H, Lq, Lk].  Sets H_Lq, the score rows that
+// share one mask row.
+const void* softmax_mask_ptr(const c10::optional<torch::Tensor>& mask,
+                             const torch::Tensor& scores, int* H_Lq) {
+  *H_Lq = 1;
+  if (!mask.has_value()) return nullptr;
+  check_f32(*mask, "mask");
+  TORCH_CHECK(scores.dim() == 4, "masked scores must be [B, H, Lq, Lk]");
+  check_shape(*mask, "mask", {scores.size(0), scores.size(3)}, "[B, Lk]");
+  *H_Lq = (int)(scores.size(1) * scores.size(2));
+  return mask->data_ptr();
+}
+
+// Optional pooling mask: bool, contiguous, on x's device, exactly [B, L].
+const void* pool_mask_ptr(const c10::optional<torch::Tensor>& mask,
+                          const torch::Tensor& x, long B, long L) {
+  if (!mask.has_value()) return nullptr;
+  TORCH_CHECK(mask->scalar_type() == torch::kBool && mask->is_contiguous(),
+              "mask must be contiguous bool");
+  TORCH_CHECK(mask->device() == x.device(), "mask must be on the same device "
+              "as the data");
+  check_shape(*mask, "mask", {B, L}, "[B, L]");
+  return mask->data_ptr();
+}
+
+// One column-sum chain (csrc/colsum.hip): ws [R, W] f32 -> [W], f32 or, with
+// out_bf16, bf16 rounded by the final stage.  split_w is the width the split
+// count derives from: W, or the narrower width of a layout that slabs were
+// appended to, which keeps the earlier slabs' sums bit-identical.
+torch::Tensor colsum(const torch::Tensor& ws, long split_w, bool out_bf16) {
+  const long R = ws.size(0), W = ws.size(1);
+  auto out = torch::empty(
+      {W}, out_bf16 ? ws.options().dtype(torch::kBFloat16) : ws.options());
+  auto scratch = torch::empty({colsum_scratch_rows(), W}, ws.options());
+  CHECK_HIP(colsum_launch(ws.data_ptr(), scratch.data_ptr(), out.data_ptr(),
+                          (int)R, (int)W, (int)split_w, out_bf16 ? 1 : 0,
+                          cur_stream()));
+  return out;
 }
 
 // ---- flash-attention argument checks ----------------------------------------
@@ -219,17 +195,20 @@ std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x,
   const int D = (int)x.size(-1);
   const long N = x.numel() / D;
   TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8, got ", D);
+  check_numel(gamma, "gamma", D, "[D]");
+  check_numel(beta, "beta", D, "[D]");
+  if (residual.has_value()) {
+    check_bf16(*residual, "residual");
+    TORCH_CHECK(residual->sizes() == x.sizes(), "residual shape mismatch");
+  }
   auto y = torch::empty_like(x);
   auto opts = x.options().dtype(torch::kFloat32);
   auto mean = torch::empty({N}, opts);
   auto rstd = torch::empty({N}, opts);
-  int grid = (int)std::min<long>((N + 3) / 4, 4096);
   const void* res_ptr = nullptr;
   torch::Tensor s_out;
   void* s_ptr = nullptr;
   if (residual.has_value()) {
-    check_bf16(*residual, "residual");
-    TORCH_CHECK(residual->sizes() == x.sizes(), "residual shape mismatch");
     res_ptr = residual->data_ptr();
     s_out = torch::empty_like(x);
     s_ptr = s_out.data_ptr();
@@ -239,7 +218,7 @@ std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x,
   CHECK_HIP(ln_fwd_launch(x.data_ptr(), res_ptr, gamma.data_ptr(),
                           beta.data_ptr(), y.data_ptr(), s_ptr,
                           mean.data_ptr(), rstd.data_ptr(), (int)N, D,
-                          (float)eps, grid, cur_stream()));
+                          (float)eps, cur_stream()));
   return {y, s_out, mean, rstd};
 }
 
@@ -258,38 +237,25 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
   const long N = x.numel() / D;
   TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8, got ", D);
   TORCH_CHECK(dy.numel() == x.numel(), "dy shape mismatch");
-  TORCH_CHECK(gamma.numel() == D, "gamma must be [D]");
+  check_numel(gamma, "gamma", D, "[D]");
   check_f32(mean, "mean"); check_f32(rstd, "rstd");
   TORCH_CHECK(mean.numel() == N && rstd.numel() == N,
               "mean and rstd must be [N]");
-  auto dx = torch::empty_like(x);
-  // bwd grid stays modest: the [rows, n * D] partials workspace and its
-  // column-sum scale linearly with the grid
-  // (D > 4096 keeps one row per WAVE in global memory: a quarter of the grid)
-  int grid = (int)std::min<long>((N + 3) / 4, D > 4096 ? 256 : 1024);
-  // one ws row per block (per wave on the wide path); either way the rows
-  // are reduced in fixed order
-  long ws_rows = ln_bwd_ws_rows(D, grid);
-  const int n_out = want_dres ? 3 : 2;
-  const int W = n_out * D;
-  auto opts = x.options().dtype(torch::kFloat32);
-  auto ws = torch::empty({ws_rows, W}, opts);
   const void* de = nullptr;
   if (ds_extra.has_value()) {
     check_bf16(*ds_extra, "ds_extra");
     TORCH_CHECK(ds_extra->numel() == x.numel(), "ds_extra shape mismatch");
     de = ds_extra->data_ptr();
   }
+  auto dx = torch::empty_like(x);
+  const int n_out = want_dres ? 3 : 2;
+  auto ws = torch::empty({ln_bwd_ws_rows((int)N, D), n_out * D},
+                         x.options().dtype(torch::kFloat32));
   CHECK_HIP(ln_bwd_launch(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(),
                           mean.data_ptr(), rstd.data_ptr(), de, dx.data_ptr(),
-                          ws.data_ptr(), n_out, (int)N, D, grid,
-                          cur_stream()));
-  auto cols = torch::empty({W}, out_bf16 ? x.options() : opts);
-  auto scratch = torch::empty({256 + 16, W}, opts);
+                          ws.data_ptr(), n_out, (int)N, D, cur_stream()));
   // splits from the two-slab width, with or without the third slab
-  CHECK_HIP(colsum_launch(ws.data_ptr(), scratch.data_ptr(), cols.data_ptr(),
-                          (int)ws_rows, W, 2 * D, out_bf16 ? 1 : 0,
-                          cur_stream()));
+  auto cols = colsum(ws, 2 * D, out_bf16);
   std::vector<torch::Tensor> out = {dx, cols.narrow(0, 0, D),
                                     cols.narrow(0, D, D)};
   if (want_dres) out.push_back(cols.narrow(0, 2 * D, D));
@@ -301,14 +267,10 @@ torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor b) {
   const int D = (int)x.size(-1);
   const long n = x.numel();
   TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8");
+  check_numel(b, "b", D, "[D]");
   auto y = torch::empty_like(x);
-  // 32 elements per thread per iteration (BG_PK=4 in bias_gelu.hip); round
-  // the grid so the stride grid*256*32 is a multiple of D (fast path)
-  int grid = (int)std::min<long>((n / 32 + 255) / 256, 4096);
-  long g0f = D / std::__gcd((long)D, 8192L);
-  if (g0f <= 2048) grid = (int)((grid + g0f - 1) / g0f * g0f);
   CHECK_HIP(bias_gelu_fwd_launch(x.data_ptr(), b.data_ptr(), y.data_ptr(), n,
-                                 D, grid, cur_stream()));
+                                 D, cur_stream()));
   return y;
 }
 
@@ -319,24 +281,15 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
   const int D = (int)x.size(-1);
   const long n = x.numel();
   TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8");
+  check_numel(b, "b", D, "[D]");
+  TORCH_CHECK(dy.numel() == x.numel(), "dy shape mismatch");
   auto dx = torch::empty_like(x);
-  int grid = (int)std::min<long>((n / 32 + 255) / 256, 1024);
-  // round the grid up to a multiple of D/gcd(D, 256*32) so the kernel's
-  // grid stride is a multiple of D -> fixed per-thread column window
-  long g = std::__gcd((long)D, 8192L);
-  long g0 = D / g;
-  if (g0 <= 2048) grid = (int)((grid + g0 - 1) / g0 * g0);
-  auto ws = torch::empty({grid, D}, x.options().dtype(torch::kFloat32));
+  auto ws = torch::empty({bias_gelu_bwd_ws_rows(n, D), D},
+                         x.options().dtype(torch::kFloat32));
   CHECK_HIP(bias_gelu_bwd_launch(dy.data_ptr(), x.data_ptr(), b.data_ptr(),
-                                 dx.data_ptr(), ws.data_ptr(), n, D, grid,
+                                 dx.data_ptr(), ws.data_ptr(), n, D,
                                  cur_stream()));
-  auto dbias = torch::empty(
-      {D}, out_bf16 ? x.options() : x.options().dtype(torch::kFloat32));
-  auto scratch = torch::empty({256 + 16, D},
-                             x.options().dtype(torch::kFloat32));
-  CHECK_HIP(colsum_launch(ws.data_ptr(), scratch.data_ptr(), dbias.data_ptr(),
-                          grid, D, D, out_bf16 ? 1 : 0, cur_stream()));
-  return {dx, dbias};
+  return {dx, colsum(ws, D, out_bf16)};
 }
 
 torch::Tensor softmax_fwd(torch::Tensor scores, c10::optional<torch::Tensor> mask,
@@ -344,21 +297,12 @@ torch::Tensor softmax_fwd(torch::Tensor scores, c10::optional<torch::Tensor> mas
   check_bf16(scores, "scores");
   const int Lk = (int)scores.size(-1);
   const long n_rows = scores.numel() / Lk;
-  TORCH_CHECK(Lk % 8 == 0, "Lk must be a multiple of 8");
-  int H_Lq = 1;
-  const void* mptr = nullptr;
-  if (mask.has_value()) {
-    check_f32(*mask, "mask");
-    TORCH_CHECK(scores.dim() == 4, "masked softmax expects [B,H,Lq,Lk]");
-    TORCH_CHECK(mask->size(0) == scores.size(0) && mask->size(-1) == Lk,
-                "mask must be [B,Lk]");
-    H_Lq = (int)(scores.size(1) * scores.size(2));
-    mptr = mask->data_ptr();
-  }
+  check_mult8(Lk, "Lk");
+  int H_Lq;
+  const void* mptr = softmax_mask_ptr(mask, scores, &H_Lq);
   auto p = torch::empty_like(scores);
-  int grid = (int)std::min<long>((n_rows + 3) / 4, 2048);
   CHECK_HIP(softmax_fwd_launch(scores.data_ptr(), mptr, p.data_ptr(), n_rows,
-                               Lk, H_Lq, (float)scale, grid, cur_stream()));
+                               Lk, H_Lq, (float)scale, cur_stream()));
   return p;
 }
 
@@ -366,10 +310,11 @@ torch::Tensor softmax_bwd(torch::Tensor dp, torch::Tensor p, double scale) {
   check_bf16(dp, "dp"); check_bf16(p, "p");
   const int Lk = (int)p.size(-1);
   const long n_rows = p.numel() / Lk;
+  check_mult8(Lk, "Lk");
+  TORCH_CHECK(dp.sizes() == p.sizes(), "dp must match p's shape");
   auto ds = torch::empty_like(p);
-  int grid = (int)std::min<long>((n_rows + 3) / 4, 2048);
   CHECK_HIP(softmax_bwd_launch(dp.data_ptr(), p.data_ptr(), ds.data_ptr(),
-                               n_rows, Lk, (float)scale, grid, cur_stream()));
+                               n_rows, Lk, (float)scale, cur_stream()));
   return ds;
 }
 
@@ -387,11 +332,10 @@ void adamw_step(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
   TORCH_CHECK(n % 4 == 0, "flat parameter buffer must be padded to 4 elems");
   TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n &&
               master.numel() == n, "size mismatch");
-  int grid = (int)std::min<long>((n / 4 + 255) / 256, 2048);
   CHECK_HIP(adamw_launch(p.data_ptr(), grad.data_ptr(), gf32, m.data_ptr(),
                          v.data_ptr(), master.data_ptr(), n, (float)lr,
                          (float)beta1, (float)beta2, (float)eps, (float)wd,
-                         (int)step, (float)grad_scale, grid, cur_stream()));
+                         (int)step, (float)grad_scale, cur_stream()));
 }
 
 // The flat gradient buffer of the clipped step: bf16 or f32, contiguous, a
@@ -437,31 +381,41 @@ void adamw_step_clipped(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
   const long n = p.numel();
   TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n &&
               master.numel() == n, "size mismatch");
-  int grid = (int)std::min<long>((n / 4 + 255) / 256, 2048);
   CHECK_HIP(adamw_clipped_launch(p.data_ptr(), grad.data_ptr(), gf32,
                                  m.data_ptr(), v.data_ptr(),
                                  master.data_ptr(), n, (float)lr,
                                  (float)beta1, (float)beta2, (float)eps,
                                  (float)wd, (int)step, clip_state.data_ptr(),
-                                 grid, cur_stream()));
+                                 cur_stream()));
 }
 
 torch::Tensor qkv_repack(torch::Tensor qkv, long H, bool backward) {
   check_bf16(qkv, "qkv");
+  TORCH_CHECK(H > 0, "H must be positive");
   long B, L, dh;
-  torch::Tensor out;
   if (!backward) {
     // [B, L, 3*H*dh] or [B, L, 3, H, dh] -> [3, B, H, L, dh]
+    TORCH_CHECK(qkv.dim() == 3 || qkv.dim() == 5,
+                "qkv must be [B, L, 3*H*dh] or [B, L, 3, H, dh]");
     B = qkv.size(0); L = qkv.size(1);
-    dh = qkv.numel() / (B * L * 3 * H);
-    out = torch::empty({3, B, H, L, dh}, qkv.options());
+    if (qkv.dim() == 3) {
+      TORCH_CHECK(qkv.size(2) % (3 * H) == 0,
+                  "qkv last dim must divide evenly by 3*H");
+      dh = qkv.size(2) / (3 * H);
+    } else {
+      check_shape(qkv, "qkv", {B, L, 3, H, qkv.size(4)}, "[B, L, 3, H, dh]");
+      dh = qkv.size(4);
+    }
   } else {
     // grad [3, B, H, L, dh] -> [B, L, 3*H*dh]
+    TORCH_CHECK(qkv.dim() == 5, "qkv grad must be [3, B, H, L, dh]");
     B = qkv.size(1); L = qkv.size(3);
     dh = qkv.size(4);
-    out = torch::empty({B, L, 3 * H * dh}, qkv.options());
+    check_shape(qkv, "qkv grad", {3, B, H, L, dh}, "[3, B, H, L, dh]");
   }
-  TORCH_CHECK(dh % 8 == 0, "head_dim must be a multiple of 8");
+  check_mult8(dh, "head_dim");
+  auto out = backward ? torch::empty({B, L, 3 * H * dh}, qkv.options())
+                      : torch::empty({3, B, H, L, dh}, qkv.options());
   CHECK_HIP(qkv_repack_launch(qkv.data_ptr(), out.data_ptr(), (int)B, (int)L,
                               (int)H, (int)dh, backward ? 1 : 0,
                               cur_stream()));
@@ -471,7 +425,11 @@ torch::Tensor qkv_repack(torch::Tensor qkv, long H, bool backward) {
 torch::Tensor qkv_repack_bwd3(torch::Tensor dq, torch::Tensor dk,
                               torch::Tensor dv) {
   check_bf16(dq, "dq"); check_bf16(dk, "dk"); check_bf16(dv, "dv");
+  TORCH_CHECK(dq.dim() == 4, "dq must be [B, H, L, dh]");
+  TORCH_CHECK(dk.sizes() == dq.sizes(), "dk must match dq's shape");
+  TORCH_CHECK(dv.sizes() == dq.sizes(), "dv must match dq's shape");
   long B = dq.size(0), H = dq.size(1), L = dq.size(2), dh = dq.size(3);
+  check_mult8(dh, "head_dim");
   auto out = torch::empty({B, L, 3 * H * dh}, dq.options());
   CHECK_HIP(qkv_repack_bwd3_launch(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
                                    out.data_ptr(), (int)B, (int)L, (int)H,
@@ -479,27 +437,28 @@ torch::Tensor qkv_repack_bwd3(torch::Tensor dq, torch::Tensor dk,
   return out;
 }
 
+// [B, H, L, dh] -> [B, L, H*dh]
 torch::Tensor out_repack(torch::Tensor x, bool backward) {
   check_bf16(x, "x");
-  long B, L, H, dh;
-  torch::Tensor out;
-  if (!backward) {
-    // [B, H, L, dh] -> [B, L, H*dh]
-    B = x.size(0); H = x.size(1); L = x.size(2); dh = x.size(3);
-    out = torch::empty({B, L, H * dh}, x.options());
-  } else {
-    TORCH_CHECK(false, "pass the 4-D grad with explicit dims via out_repack_bwd");
-  }
-  TORCH_CHECK(dh % 8 == 0, "head_dim must be a multiple of 8");
+  TORCH_CHECK(!backward,
+              "pass the 4-D grad with explicit dims via out_repack_bwd");
+  TORCH_CHECK(x.dim() == 4, "x must be [B, H, L, dh]");
+  long B = x.size(0), H = x.size(1), L = x.size(2), dh = x.size(3);
+  check_mult8(dh, "head_dim");
+  auto out = torch::empty({B, L, H * dh}, x.options());
   CHECK_HIP(out_repack_launch(x.data_ptr(), out.data_ptr(), (int)B, (int)L,
                               (int)H, (int)dh, 0, cur_stream()));
   return out;
 }
 
+// [B, L, H*dh] -> [B, H, L, dh]
 torch::Tensor out_repack_bwd(torch::Tensor dgrad, long H) {
   check_bf16(dgrad, "dgrad");
-  long B = dgrad.size(0), L = dgrad.size(1);
-  long dh = dgrad.numel() / (B * L * H);
+  TORCH_CHECK(dgrad.dim() == 3, "dgrad must be [B, L, H*dh]");
+  TORCH_CHECK(H > 0 && dgrad.size(2) % H == 0,
+              "dgrad last dim must divide evenly by H");
+  long B = dgrad.size(0), L = dgrad.size(1), dh = dgrad.size(2) / H;
+  check_mult8(dh, "head_dim");
   auto out = torch::empty({B, H, L, dh}, dgrad.options());
   CHECK_HIP(out_repack_launch(dgrad.data_ptr(), out.data_ptr(), (int)B,
                               (int)L, (int)H, (int)dh, 1, cur_stream()));
@@ -528,18 +487,13 @@ torch::Tensor p_from_lse(torch::Tensor scores, c10::optional<torch::Tensor> mask
   const int Lk = (int)scores.size(-1);
   const long n_rows = scores.numel() / Lk;
   TORCH_CHECK(lse.numel() == n_rows, "lse size mismatch");
-  int H_Lq = 1;
-  const void* mptr = nullptr;
-  if (mask.has_value()) {
-    check_f32(*mask, "mask");
-    H_Lq = (int)(scores.size(1) * scores.size(2));
-    mptr = mask->data_ptr();
-  }
+  check_mult8(Lk, "Lk");
+  int H_Lq;
+  const void* mptr = softmax_mask_ptr(mask, scores, &H_Lq);
   auto p = torch::empty_like(scores);
-  int grid = (int)std::min<long>((n_rows + 3) / 4, 2048);
   CHECK_HIP(p_from_lse_launch(scores.data_ptr(), mptr, lse.data_ptr(),
                               p.data_ptr(), n_rows, Lk, H_Lq, (float)scale,
-                              grid, cur_stream()));
+                              cur_stream()));
   return p;
 }
 
@@ -617,8 +571,9 @@ torch::Tensor bias_grad(torch::Tensor dy) {
   check_bf16(dy, "dy");
   const int D = (int)dy.size(-1);
   const long N = dy.numel() / D;
+  TORCH_CHECK(dy.dim() == 2, "dy must be [N, D]");
   TORCH_CHECK(D % 8 == 0, "D % 8 == 0 required");
-  auto scratch = torch::empty({1024 + 16, D},
+  auto scratch = torch::empty({colsum_bf16_scratch_rows(), D},
                               dy.options().dtype(torch::kFloat32));
   auto out = torch::empty({D}, dy.options());
   CHECK_HIP(colsum_bf16_launch(dy.data_ptr(), scratch.data_ptr(),
@@ -649,7 +604,7 @@ namespace {
 // With want_bias also dqkv_bias [3D] bf16, the column sum of dqkv over all
 // B * L rows (the qkv projection's bias gradient): both kernels emit
 // per-workgroup column partials of what they store into one
-// [B * ceil(L / 128), 3D] f32 workspace and one colsum chain reduces it.
+// [flash_bias_ws_rows(B, L), 3D] f32 workspace and one colsum chain reduces it.
 std::vector<torch::Tensor> flash_bwd_packed_impl(
     torch::Tensor qkv, torch::Tensor o, torch::Tensor dout,
     c10::optional<torch::Tensor> mask, torch::Tensor lse, long H,
@@ -664,13 +619,11 @@ std::vector<torch::Tensor> flash_bwd_packed_impl(
                                  ddot.data_ptr(), (int)B, (int)H, (int)L,
                                  cur_stream()));
   auto dqkv = torch::empty_like(qkv);
-  const auto f32 = qkv.options().dtype(torch::kFloat32);
-  const long W = 3 * H * 64;
-  const long ws_rows = B * ((L + 127) / 128);
   torch::Tensor ws;
   void* ws_ptr = nullptr;
   if (want_bias) {
-    ws = torch::empty({ws_rows, W}, f32);
+    ws = torch::empty({flash_bias_ws_rows((int)B, (int)L), 3 * H * 64},
+                      qkv.options().dtype(torch::kFloat32));
     ws_ptr = ws.data_ptr();
   }
   CHECK_HIP(flash_bwd_fused_packed_launch(
@@ -682,11 +635,7 @@ std::vector<torch::Tensor> flash_bwd_packed_impl(
       ddot.data_ptr(), dqkv.data_ptr(), ws_ptr, (int)B, (int)H, (int)L,
       (float)scale, cur_stream()));
   if (!want_bias) return {dqkv};
-  auto dbias = torch::empty({W}, qkv.options());
-  auto scratch = torch::empty({256 + 16, W}, f32);
-  CHECK_HIP(colsum_launch(ws.data_ptr(), scratch.data_ptr(), dbias.data_ptr(),
-                          (int)ws_rows, (int)W, (int)W, 1, cur_stream()));
-  return {dqkv, dbias};
+  return {dqkv, colsum(ws, ws.size(1), true)};
 }
 
 }  // namespace
@@ -744,16 +693,12 @@ std::vector<torch::Tensor> masked_pool_fwd(torch::Tensor x,
   check_bf16(x, "x");
   TORCH_CHECK(x.dim() == 3, "x must be [B, L, D]");
   long B = x.size(0), L = x.size(1), D = x.size(2);
-  TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8");
-  const void* mptr = nullptr;
-  if (mask.has_value()) {
-    TORCH_CHECK(mask->scalar_type() == torch::kBool && mask->is_contiguous(),
-                "mask must be contiguous bool");
-    mptr = mask->data_ptr();
-  }
+  check_mult8(D, "D");
+  const void* mptr = pool_mask_ptr(mask, x, B, L);
   auto pooled = torch::empty({B, D}, x.options());
   auto counts = torch::empty({B}, x.options().dtype(torch::kFloat32));
-  auto ws = torch::empty({B, 16, D}, x.options().dtype(torch::kFloat32));
+  auto ws = torch::empty({B, masked_pool_ws_splits(), D},
+                         x.options().dtype(torch::kFloat32));
   CHECK_HIP(masked_pool_fwd_launch(x.data_ptr(), mptr, pooled.data_ptr(),
                                    counts.data_ptr(), ws.data_ptr(), (int)B,
                                    (int)L, (int)D, cur_stream()));
@@ -764,9 +709,13 @@ torch::Tensor masked_pool_bwd(torch::Tensor dpooled,
                               c10::optional<torch::Tensor> mask,
                               torch::Tensor counts, long L) {
   check_bf16(dpooled, "dpooled");
+  TORCH_CHECK(dpooled.dim() == 2, "dpooled must be [B, D]");
   long B = dpooled.size(0), D = dpooled.size(1);
-  const void* mptr = nullptr;
-  if (mask.has_value()) mptr = mask->data_ptr();
+  check_mult8(D, "D");
+  TORCH_CHECK(L > 0, "L must be positive");
+  check_f32(counts, "counts");
+  check_shape(counts, "counts", {B}, "[B]");
+  const void* mptr = pool_mask_ptr(mask, dpooled, B, L);
   auto dx = torch::empty({B, L, D}, dpooled.options());
   CHECK_HIP(masked_pool_bwd_launch(dpooled.data_ptr(), mptr,
                                    counts.data_ptr(), dx.data_ptr(), (int)B,

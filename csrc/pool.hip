@@ -9,6 +9,7 @@
 // The per-segment pool of packed batches is at the end of the file.
 
 #include "common.h"
+#include "launchers.h"
 
 #define PL_BLOCK 256
 
@@ -99,6 +100,9 @@ masked_pool_bwd_kernel(const short* __restrict__ dpooled,
     }
   }
 }
+
+// ws is [B, PL_SPLITS, D] f32; the bindings ask for the split count.
+extern "C" int masked_pool_ws_splits(void) { return PL_SPLITS; }
 
 extern "C" hipError_t masked_pool_fwd_launch(const void* x, const void* mask,
                                              void* pooled, void* counts,

@@ -12,6 +12,7 @@
 // source and destination visits are coalesced along dh.
 
 #include "common.h"
+#include "launchers.h"
 
 #define RP_BLOCK 256
 

@@ -10,10 +10,19 @@
 // Classifier uses Lk in {128, 512}; general loop covers larger Lk.
 
 #include "common.h"
+#include "launchers.h"
 
 #define SM_WPB 4
 #define SM_BLOCK (SM_WPB * WAVE)
 #define MAX_SM_PKT 4  // register path for Lk <= 2048
+
+// Launch geometry of all three row kernels: one wave per row, grid-stride
+// past the cap.
+#define SM_MAX_GRID 2048
+static int sm_grid(long n_rows) {
+  long blocks = (n_rows + SM_WPB - 1) / SM_WPB;
+  return (int)(blocks < SM_MAX_GRID ? blocks : SM_MAX_GRID);
+}
 
 extern "C" {
 
@@ -178,16 +187,16 @@ softmax_bwd_kernel(const short* __restrict__ dp, const short* __restrict__ p_in,
 
 hipError_t softmax_fwd_launch(const void* s, const void* mask, void* p,
                               long n_rows, int Lk, int H_Lq, float scale,
-                              int grid, hipStream_t stream) {
-  softmax_fwd_kernel<<<grid, SM_BLOCK, 0, stream>>>(
+                              hipStream_t stream) {
+  softmax_fwd_kernel<<<sm_grid(n_rows), SM_BLOCK, 0, stream>>>(
       (const short*)s, (const float*)mask, (short*)p, n_rows, Lk, H_Lq, scale);
   return hipGetLastError();
 }
 
 hipError_t softmax_bwd_launch(const void* dp, const void* p, void* ds,
-                              long n_rows, int Lk, float scale, int grid,
+                              long n_rows, int Lk, float scale,
                               hipStream_t stream) {
-  softmax_bwd_kernel<<<grid, SM_BLOCK, 0, stream>>>(
+  softmax_bwd_kernel<<<sm_grid(n_rows), SM_BLOCK, 0, stream>>>(
       (const short*)dp, (const short*)p, (short*)ds, n_rows, Lk, scale);
   return hipGetLastError();
 }
@@ -230,8 +239,8 @@ p_from_lse_kernel(const short* __restrict__ s_in, const float* __restrict__ mask
 extern "C" hipError_t p_from_lse_launch(const void* s, const void* mask,
                                         const void* lse, void* p, long n_rows,
                                         int Lk, int H_Lq, float scale,
-                                        int grid, hipStream_t stream) {
-  p_from_lse_kernel<<<grid, SM_BLOCK, 0, stream>>>(
+                                        hipStream_t stream) {
+  p_from_lse_kernel<<<sm_grid(n_rows), SM_BLOCK, 0, stream>>>(
       (const short*)s, (const float*)mask, (const float*)lse, (short*)p,
       n_rows, Lk, H_Lq, scale);
   return hipGetLastError();

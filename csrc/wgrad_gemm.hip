@@ -28,6 +28,7 @@
 // SURVEY.md §2.1); this backs the MLTC classifier lane's training step.
 
 #include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;

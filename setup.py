@@ -26,6 +26,7 @@ ext = CUDAExtension(
         "csrc/ops.cpp",
         "csrc/lt_gemm.cpp",
         "csrc/layernorm.hip",
+        "csrc/colsum.hip",
         "csrc/bias_gelu.hip",
         "csrc/softmax.hip",
         "csrc/adamw.hip",

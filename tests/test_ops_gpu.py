@@ -343,6 +343,143 @@ def test_flash_rejects_wrong_mask_and_lse_shapes():
         ext.flash_bwd_packed(qkv, o_p, do_p, None, bad_lse, H, scale)
 
 
+# The non-flash bindings pin their operands the same way.  Each test below
+# makes one valid call at the smallest legal shape, then malformed ones that
+# the binding must refuse by name before anything is allocated or launched.
+
+def test_layernorm_rejects_wrong_param_shapes():
+    ext = ops.hip_ops()
+    N, D = 4, 8
+    x, dy = _bf16(torch.randn(N, D)), _bf16(torch.randn(N, D))
+    g, b = _bf16(torch.ones(D)), _bf16(torch.zeros(D))
+    g16, b16 = _bf16(torch.ones(16)), _bf16(torch.zeros(16))
+    y, _, mean, rstd = ext.layernorm_fwd(x, None, g, b, 1e-5)
+    assert y.shape == x.shape
+    assert ext.layernorm_bwd(dy, x, g, mean, rstd, None)[0].shape == x.shape
+    with pytest.raises(RuntimeError, match="gamma"):
+        ext.layernorm_fwd(x, None, g16, b, 1e-5)
+    with pytest.raises(RuntimeError, match="beta"):
+        ext.layernorm_fwd(x, None, g, b16, 1e-5)
+    with pytest.raises(RuntimeError, match="gamma"):
+        ext.layernorm_bwd(dy, x, g16, mean, rstd, None)
+
+
+def test_bias_gelu_rejects_wrong_bias_and_grad_shapes():
+    ext = ops.hip_ops()
+    N, D = 4, 8
+    x, dy = _bf16(torch.randn(N, D)), _bf16(torch.randn(N, D))
+    b, b16 = _bf16(torch.zeros(D)), _bf16(torch.zeros(16))
+    assert ext.bias_gelu_fwd(x, b).shape == x.shape
+    dx, dbias = ext.bias_gelu_bwd(dy, x, b)
+    assert dx.shape == x.shape and dbias.shape == (D,)
+    with pytest.raises(RuntimeError, match=r"\bb must be"):
+        ext.bias_gelu_fwd(x, b16)
+    with pytest.raises(RuntimeError, match=r"\bb must be"):
+        ext.bias_gelu_bwd(dy, x, b16)
+    with pytest.raises(RuntimeError, match="dy"):
+        ext.bias_gelu_bwd(_bf16(torch.randn(N // 2, D)), x, b)
+
+
+def test_bias_grad_rejects_non_2d():
+    ext = ops.hip_ops()
+    assert ext.bias_grad(_bf16(torch.randn(4, 8))).shape == (8,)
+    with pytest.raises(RuntimeError, match="dy"):
+        ext.bias_grad(_bf16(torch.randn(2, 2, 8)))
+
+
+def test_softmax_rejects_wrong_mask_and_grad_shapes():
+    ext = ops.hip_ops()
+    s = _bf16(torch.randn(1, 1, 4, 8))
+    mask = torch.zeros(1, 8, device="cuda")
+    wide = torch.zeros(1, 16, device="cuda")    # Lk mismatch
+    tall = torch.zeros(2, 8, device="cuda")     # B mismatch
+    lse = torch.zeros(1, 1, 4, device="cuda")
+    p = ext.softmax_fwd(s, mask, 1.0)
+    assert p.shape == s.shape
+    assert ext.softmax_bwd(_bf16(torch.randn(1, 1, 4, 8)), p, 1.0).shape == \
+        s.shape
+    assert ext.p_from_lse(s, mask, lse, 1.0).shape == s.shape
+    for bad in (wide, tall, mask.view(1, 1, 8)):
+        with pytest.raises(RuntimeError, match="mask"):
+            ext.softmax_fwd(s, bad, 1.0)
+        with pytest.raises(RuntimeError, match="mask"):
+            ext.p_from_lse(s, bad, lse, 1.0)
+    with pytest.raises(RuntimeError, match="scores"):
+        ext.p_from_lse(s.view(4, 8), mask, lse, 1.0)
+    with pytest.raises(RuntimeError, match="dp"):
+        ext.softmax_bwd(_bf16(torch.randn(1, 1, 2, 8)), p, 1.0)
+    s4 = _bf16(torch.randn(1, 1, 4, 4))
+    with pytest.raises(RuntimeError, match="Lk"):
+        ext.softmax_bwd(s4, s4, 1.0)
+    with pytest.raises(RuntimeError, match="Lk"):
+        ext.p_from_lse(s4, None, lse, 1.0)
+
+
+def test_masked_pool_rejects_wrong_mask_and_counts():
+    ext = ops.hip_ops()
+    B, L, D = 2, 4, 8
+    x, dp = _bf16(torch.randn(B, L, D)), _bf16(torch.randn(B, D))
+    mask = torch.ones(B, L, dtype=torch.bool, device="cuda")
+    pooled, counts = ext.masked_pool_fwd(x, mask)
+    assert pooled.shape == (B, D) and counts.shape == (B,)
+    assert ext.masked_pool_bwd(dp, mask, counts, L).shape == x.shape
+    bad_masks = (torch.ones(B, 8, dtype=torch.bool, device="cuda"),
+                 torch.ones(B, L, dtype=torch.int32, device="cuda"),
+                 torch.ones(B, L, dtype=torch.bool))          # on the host
+    for bad in bad_masks:
+        with pytest.raises(RuntimeError, match="mask"):
+            ext.masked_pool_fwd(x, bad)
+        with pytest.raises(RuntimeError, match="mask"):
+            ext.masked_pool_bwd(dp, bad, counts, L)
+    for bad in (torch.ones(3, device="cuda"), counts.to(torch.bfloat16)):
+        with pytest.raises(RuntimeError, match="counts"):
+            ext.masked_pool_bwd(dp, mask, bad, L)
+    with pytest.raises(RuntimeError, match="dpooled"):
+        ext.masked_pool_bwd(dp.view(B, 1, D), mask, counts, L)
+    with pytest.raises(RuntimeError, match="L must be"):
+        ext.masked_pool_bwd(dp, None, counts, 0)
+
+
+def test_repack_rejects_wrong_ranks_and_shapes():
+    ext = ops.hip_ops()
+    B, L, H, dh = 1, 4, 2, 8
+    qkv = _bf16(torch.randn(B, L, 3 * H * dh))
+    q3 = ext.qkv_repack(qkv, H, False)
+    assert q3.shape == (3, B, H, L, dh)
+    dq, dk, dv = (t.contiguous() for t in q3.unbind(0))
+    assert torch.equal(ext.qkv_repack_bwd3(dq, dk, dv), qkv)
+    merged = ext.out_repack(dq, False)
+    assert merged.shape == (B, L, H * dh)
+    assert torch.equal(ext.out_repack_bwd(merged, H), dq)
+    other = _bf16(torch.randn(B, H, L, 2 * dh))
+    with pytest.raises(RuntimeError, match="dk"):
+        ext.qkv_repack_bwd3(dq, other, dv)
+    with pytest.raises(RuntimeError, match="dv"):
+        ext.qkv_repack_bwd3(dq, dk, other)
+    with pytest.raises(RuntimeError, match="dq"):
+        ext.qkv_repack_bwd3(dq[0], dk[0], dv[0])
+    with pytest.raises(RuntimeError, match="qkv"):
+        ext.qkv_repack(qkv, 5, False)             # 48 % (3 * 5) != 0
+    with pytest.raises(RuntimeError, match="qkv"):
+        ext.qkv_repack(qkv.view(B, L, 3, H * dh), H, False)
+    with pytest.raises(RuntimeError, match="x must be"):
+        ext.out_repack(merged, False)
+    with pytest.raises(RuntimeError, match="dgrad"):
+        ext.out_repack_bwd(merged, 3)             # 16 % 3 != 0
+    with pytest.raises(RuntimeError, match="dgrad"):
+        ext.out_repack_bwd(dq, H)
+    # head_dim 4: every one of the four refuses it
+    half = _bf16(torch.randn(B, H, L, 4))
+    with pytest.raises(RuntimeError, match="head_dim"):
+        ext.qkv_repack(_bf16(torch.randn(B, L, 3 * H * 4)), H, False)
+    with pytest.raises(RuntimeError, match="head_dim"):
+        ext.qkv_repack_bwd3(half, half, half)
+    with pytest.raises(RuntimeError, match="head_dim"):
+        ext.out_repack(half, False)
+    with pytest.raises(RuntimeError, match="head_dim"):
+        ext.out_repack_bwd(_bf16(torch.randn(B, L, H * 4)), H)
+
+
 def test_layernorm_bwd_with_residual_grad():
     torch.manual_seed(15)
     N, D = 64, 1024

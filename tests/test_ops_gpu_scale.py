@@ -1,7 +1,8 @@
 """Elementwise kernels at training sizes, against the fp32 reference.
 
 LayerNorm, bias+GeLU, softmax, the pools and AdamW are persistent
-grid-stride kernels whose grids are capped in csrc/ops.cpp.  The shapes here
+grid-stride kernels whose grids are capped by their launchers, each in the
+kernel's own csrc/*.hip file.  The shapes here
 are the smallest that send a wave round its loop a second time with a ragged
 tail, at every config width (D = 128, 512, 1024, 2048), plus five-launch
 bitwise reproducibility of the two reductions that merge across waves.

@@ -241,7 +241,7 @@ def out_repack(x):
 
 class _LinearFn(torch.autograd.Function):
     """F.linear with the bias gradient computed by the two-stage bf16
-    column-sum kernel (csrc/layernorm.hip colsum_bf16).  MEASURED NOTE: not
+    column-sum kernel (csrc/colsum.hip colsum_bf16).  MEASURED NOTE: not
     used by the model — routing the projections through this Function cost
     13.7 ms/step because the explicit dgrad/wgrad matmuls here dispatch to
     slower hipBLASLt algos than torch's addmm backward (which reaches the
