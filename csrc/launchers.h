@@ -27,6 +27,27 @@ hipError_t ln_bwd_launch(const void* dy, const void* x, const void* gamma,
                          const void* ds_extra, void* dx, void* ws, int n_out,
                          int N, int D, hipStream_t stream);
 int ln_bwd_ws_rows(int N, int D);
+// Fused residual dropout (philox.h): as ln_fwd_launch with res and s_out
+// required, s_out = bf16(x + (keep ? res * scale : 0)); as ln_bwd_launch with
+// n_out = 2 and a second output dres [N, D] bf16 = keep ? bf16(v * scale) : 0,
+// v the f32 value dx is rounded from.  seed, call, site: the mask's key and
+// counter words; thr in [1, 65535]: an element is dropped iff its 16 random
+// bits are below thr, scale = 65536 / (65536 - thr).  The backward takes
+// D <= ln_drop_bwd_max_d() and sizes ws with ln_bwd_ws_rows.
+hipError_t ln_drop_fwd_launch(const void* x, const void* res,
+                              const void* gamma, const void* beta, void* y,
+                              void* s_out, void* mean, void* rstd, int N,
+                              int D, float eps, unsigned long long seed,
+                              unsigned call, unsigned site, unsigned thr,
+                              hipStream_t stream);
+hipError_t ln_drop_bwd_launch(const void* dy, const void* x,
+                              const void* gamma, const void* mean,
+                              const void* rstd, const void* ds_extra, void* dx,
+                              void* dres, void* ws, int N, int D,
+                              unsigned long long seed, unsigned call,
+                              unsigned site, unsigned thr,
+                              hipStream_t stream);
+int ln_drop_bwd_max_d(void);
 
 // ---- colsum.hip -------------------------------------------------------------
 // ws [R, D] f32 -> out [D] (f32, or bf16 with out_bf16).  scratch is

@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "philox.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -22,15 +23,54 @@
 // cached path and re-read for larger D.
 #define MAX_PKT 8  // cached path handles D <= 64*8*MAX_PKT = 4096
 
-extern "C" {
+// Fused residual dropout (DROP instantiations; docs/KERNELS.md "Fused
+// residual dropout").  The keep bits of a packet come from drop_keep8
+// (philox.h), indexed by the packet's GLOBAL element offset, so the mask is
+// the same whatever the grid, the rows per wave or the kernel variant.
+//
+// Forward: the f32 stream value x + (keep ? res * scale : 0), which the
+// caller rounds to bf16 once.  Contraction is off so that the product rounds
+// to f32 before the add, as the reference's separate multiply and add do.
+__device__ __forceinline__ float drop_add(float x, float r, bool keep,
+                                          float scale) {
+#pragma clang fp contract(off)
+  float t = r * scale;
+  return x + (keep ? t : 0.f);
+}
 
+// The rounding points of ln_bwd_t2's DROP instantiations, spelled out.
+// Whether a product is fused into the add that follows it is otherwise the
+// optimizer's choice per instantiation, and the dropout instantiations must
+// return bit for bit the dx, dgamma and dbeta of their siblings, which
+// compile to: column and row sums from rounded products (no fusing), dx from
+// fused ones (ln_bwd_t2_dx below).
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// dx = rstd * (dyg - s1 - xh * s2) [+ ds_extra], both products fused.
+template <bool HASDE>
+__device__ __forceinline__ float ln_bwd_t2_dx(float dyg, float xh, float s1,
+                                              float s2, float rstd, short ve) {
+  const float t = __builtin_fmaf(-xh, s2, dyg - s1);
+  return HASDE ? __builtin_fmaf(rstd, t, bf16_to_f32(ve)) : rstd * t;
+}
+
+// Backward: dres = keep ? bf16(v * scale) : 0, v being the f32 value dx is
+// rounded from.
+__device__ __forceinline__ short drop_grad(float v, bool keep, float scale) {
+  return keep ? f32_to_bf16(v * scale) : (short)0;
+}
+
+template <bool DROP>
 __global__ void __launch_bounds__(BLOCK)
 ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
               const short* __restrict__ gamma,
               const short* __restrict__ beta, short* __restrict__ y,
               short* __restrict__ s_out,
               float* __restrict__ mean_out, float* __restrict__ rstd_out,
-              int N, int D, float eps) {
+              int N, int D, float eps, LnDrop dr) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   const int pkts = D / (WAVE * 8);  // short8 packets per lane (D % 512 == 0 fast path)
@@ -56,11 +96,16 @@ ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
         }
         if (rr) {
           short8_t rv = *(const short8_t*)(rr + base);
+          unsigned keep = 0;
+          if (DROP) keep = drop_keep8(dr, ((long)row * D + base) >> 3);
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             // bf16-rounded sum so s_out, the saved x for bwd, and the stats
             // all see the SAME residual-stream value
-            short sum_b = f32_to_bf16(vals[p * 8 + j] + bf16_to_f32(rv[j]));
+            float sum = DROP ? drop_add(vals[p * 8 + j], bf16_to_f32(rv[j]),
+                                        (keep >> j) & 1, dr.scale)
+                             : vals[p * 8 + j] + bf16_to_f32(rv[j]);
+            short sum_b = f32_to_bf16(sum);
             vals[p * 8 + j] = bf16_to_f32(sum_b);
             so[j] = sum_b;
           }
@@ -104,9 +149,14 @@ ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
         if (rr) {
           short8_t rv = *(const short8_t*)(rr + i);
           short8_t so;
+          unsigned keep = 0;
+          if (DROP) keep = drop_keep8(dr, ((long)row * D + i) >> 3);
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
-            so[j] = f32_to_bf16(bf16_to_f32(v[j]) + bf16_to_f32(rv[j]));
+            float sum = DROP ? drop_add(bf16_to_f32(v[j]), bf16_to_f32(rv[j]),
+                                        (keep >> j) & 1, dr.scale)
+                             : bf16_to_f32(v[j]) + bf16_to_f32(rv[j]);
+            so[j] = f32_to_bf16(sum);
           }
           *(short8_t*)(sr + i) = so;
           v = so;
@@ -143,19 +193,17 @@ ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
   }
 }
 
-}  // extern "C" (templates below need C++ linkage)
-
 // Template-specialized fast path: exact unroll for D = PKTS*512 (no
 // MAX_PKT-sized register waste), gamma/beta hoisted out of the row loop,
 // and the NEXT row's packets prefetched before the wave-reduction chains so
 // the loads overlap the two log2(64) shuffle reductions.  One wave per row.
-template <int PKTS, bool HASRES>
+template <int PKTS, bool HASRES, bool DROP>
 __global__ void __launch_bounds__(BLOCK)
 ln_fwd_t(const short* __restrict__ x, const short* __restrict__ res,
          const short* __restrict__ gamma, const short* __restrict__ beta,
          short* __restrict__ y, short* __restrict__ s_out,
          float* __restrict__ mean_out, float* __restrict__ rstd_out,
-         int N, int D, float eps) {
+         int N, int D, float eps, LnDrop dr) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   const int rstride = gridDim.x * WAVES_PER_BLOCK;
@@ -187,13 +235,19 @@ ln_fwd_t(const short* __restrict__ x, const short* __restrict__ res,
 #pragma unroll
     for (int p = 0; p < PKTS; ++p) {
       short8_t so;
+      unsigned keep = 0;
+      if (DROP)
+        keep = drop_keep8(dr, ((long)row * D + (p * WAVE + lane) * 8) >> 3);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float f = bf16_to_f32(vx[p][j]);
         if (HASRES) {
           // bf16-rounded sum so s_out, the saved x for bwd, and the stats
           // all see the SAME residual-stream value
-          short sum_b = f32_to_bf16(f + bf16_to_f32(vr[p][j]));
+          float sum = DROP ? drop_add(f, bf16_to_f32(vr[p][j]),
+                                      (keep >> j) & 1, dr.scale)
+                           : f + bf16_to_f32(vr[p][j]);
+          short sum_b = f32_to_bf16(sum);
           f = bf16_to_f32(sum_b);
           so[j] = sum_b;
         }
@@ -371,13 +425,16 @@ ln_bwd_t(const short* __restrict__ dy, const short* __restrict__ x,
 // shadow — the four wave_sum chains (s1/s2 x 2 rows) issue back-to-back.
 // The column accumulators are shared (summed over both rows, row A first), so
 // the workspace layout and the deterministic colsum are unchanged.
-template <int PKTS, bool HASDE, bool DRES>
+// DROP: a second output dres, the gradient of the dropped residual input
+// (drop_grad above); dx, the partials and their order are untouched.
+template <int PKTS, bool HASDE, bool DRES, bool DROP>
 __global__ void __launch_bounds__(BLOCK)
 ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
           const short* __restrict__ gamma, const float* __restrict__ mean_in,
           const float* __restrict__ rstd_in,
           const short* __restrict__ ds_extra, short* __restrict__ dx,
-          float* __restrict__ ws, int N, int D) {
+          float* __restrict__ ws, int N, int D, short* __restrict__ dres,
+          LnDrop dr) {
   constexpr int NOUT = DRES ? 3 : 2;
   __shared__ __attribute__((aligned(16))) float sm[NOUT * PKTS * WAVE * 8];
   const int lane = threadIdx.x & (WAVE - 1);
@@ -425,19 +482,19 @@ ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
         int k = p * 8 + j;
         float dA = bf16_to_f32(vdA[p][j]);
         float hA = (bf16_to_f32(vxA[p][j]) - meanA) * rstdA;
-        float gA = dA * gv[k];
+        float gA = DROP ? mul_rn(dA, gv[k]) : dA * gv[k];
         xhA[k] = hA; dygA[k] = gA;
-        acc[0][k] += dA * hA;
+        acc[0][k] += DROP ? mul_rn(dA, hA) : dA * hA;
         acc[1][k] += dA;
-        s1A += gA; s2A += gA * hA;
+        s1A += gA; s2A += DROP ? mul_rn(gA, hA) : gA * hA;
         if (actB) {
           float dB = bf16_to_f32(vdB[p][j]);
           float hB = (bf16_to_f32(vxB[p][j]) - meanB) * rstdB;
-          float gB = dB * gv[k];
+          float gB = DROP ? mul_rn(dB, gv[k]) : dB * gv[k];
           xhB[k] = hB; dygB[k] = gB;
-          acc[0][k] += dB * hB;
+          acc[0][k] += DROP ? mul_rn(dB, hB) : dB * hB;
           acc[1][k] += dB;
-          s1B += gB; s2B += gB * hB;
+          s1B += gB; s2B += DROP ? mul_rn(gB, hB) : gB * hB;
         }
       }
     }
@@ -461,6 +518,29 @@ ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
     }
 #pragma unroll
     for (int p = 0; p < PKTS; ++p) {
+      const int base = (p * WAVE + lane) * 8;
+      if (DROP) {
+        // one row after the other: the Philox state and the second output
+        // vector of both rows at once cost the D = 1024 instance a wave
+        // per SIMD (docs/KERNELS.md)
+        auto emit = [&](int row, const float* dyg, const float* xh,
+                        const short8_t& ve, float rstd, float s1, float s2) {
+          const unsigned keep = drop_keep8(dr, ((long)row * D + base) >> 3);
+          short8_t o, r;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float d_ = ln_bwd_t2_dx<HASDE>(dyg[p * 8 + j], xh[p * 8 + j], s1,
+                                           s2, rstd, ve[j]);
+            o[j] = f32_to_bf16(d_);
+            r[j] = drop_grad(d_, (keep >> j) & 1, dr.scale);
+          }
+          *(short8_t*)(dx + (long)row * D + base) = o;
+          *(short8_t*)(dres + (long)row * D + base) = r;
+        };
+        emit(rowA, dygA, xhA, veA[p], rstdA, s1A, s2A);
+        if (actB) emit(rowA + 1, dygB, xhB, veB[p], rstdB, s1B, s2B);
+        continue;
+      }
       short8_t oA, oB;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -477,7 +557,6 @@ ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
           if (DRES) acc[NOUT - 1][k] += bf16_to_f32(oB[j]);
         }
       }
-      int base = (p * WAVE + lane) * 8;
       *(short8_t*)(dx + (long)rowA * D + base) = oA;
       if (actB) *(short8_t*)(dx + (long)(rowA + 1) * D + base) = oB;
     }
@@ -505,13 +584,15 @@ ln_bwd_t2(const short* __restrict__ dy, const short* __restrict__ x,
 // The four waves of a block then merge their partials through LDS one wave
 // at a time, wave 0 first: every column is summed in the same order on
 // every run, with no atomics.  One ws row of NOUT * D floats per block.
-template <int MAXP, bool DRES>
+// DROP: as in ln_bwd_t2, a second output dres.
+template <int MAXP, bool DRES, bool DROP>
 __global__ void __launch_bounds__(BLOCK)
 ln_bwd_g(const short* __restrict__ dy, const short* __restrict__ x,
          const short* __restrict__ gamma, const float* __restrict__ mean_in,
          const float* __restrict__ rstd_in,
          const short* __restrict__ ds_extra,  // optional += into dx
-         short* __restrict__ dx, float* __restrict__ ws, int N, int D) {
+         short* __restrict__ dx, float* __restrict__ ws, int N, int D,
+         short* __restrict__ dres, LnDrop dr) {
   constexpr int NOUT = DRES ? 3 : 2;
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
@@ -552,18 +633,32 @@ ln_bwd_g(const short* __restrict__ dy, const short* __restrict__ x,
       if (base >= D) continue;
       short8_t ev;
       if (der) ev = *(const short8_t*)(der + base);
-      short8_t o;
+      short8_t o, r;
+      unsigned keep = 0;
+      if (DROP) keep = drop_keep8(dr, ((long)row * D + base) >> 3);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float h = (bf16_to_f32(vx[p][j]) - mean) * rstd;
         float g = bf16_to_f32(vd[p][j]) * bf16_to_f32(vg[p][j]);
-        float d_ = rstd * (g - s1 - h * s2);
-        if (der) d_ += bf16_to_f32(ev[j]);
+        float d_;
+        if (DROP) {
+          // the sibling's fusing (every product into the add after it),
+          // spelled out: see mul_rn
+          const float t = __builtin_fmaf(
+              -h, s2, __builtin_fmaf(bf16_to_f32(vd[p][j]),
+                                     bf16_to_f32(vg[p][j]), -s1));
+          d_ = der ? __builtin_fmaf(rstd, t, bf16_to_f32(ev[j])) : rstd * t;
+          r[j] = drop_grad(d_, (keep >> j) & 1, dr.scale);
+        } else {
+          d_ = rstd * (g - s1 - h * s2);
+          if (der) d_ += bf16_to_f32(ev[j]);
+        }
         o[j] = f32_to_bf16(d_);
         // the sum of what is STORED: round first, then accumulate
         if (DRES) acc[NOUT - 1][p * 8 + j] += bf16_to_f32(o[j]);
       }
       *(short8_t*)(dxr + base) = o;
+      if (DROP) *(short8_t*)(dres + (long)row * D + base) = r;
     }
   }
   // fixed-order merge: wave w adds its partials after waves 0..w-1 have
@@ -679,24 +774,27 @@ static int ln_bwd_grid(int N, int D) {
                                              : LN_BWD_MAX_GRID);
 }
 
-extern "C" {
-
-hipError_t ln_fwd_launch(const void* x, const void* res, const void* gamma,
-                         const void* beta, void* y, void* s_out, void* mean,
-                         void* rstd, int N, int D, float eps,
-                         hipStream_t stream) {
+// One dispatch per direction, shared by the plain and the dropout launchers:
+// DROP only selects the instantiation, so both take the same kernel variant
+// and the same grid at every width.
+template <bool DROP>
+static hipError_t ln_fwd_dispatch(const void* x, const void* res,
+                                  const void* gamma, const void* beta, void* y,
+                                  void* s_out, void* mean, void* rstd, int N,
+                                  int D, float eps, LnDrop dr,
+                                  hipStream_t stream) {
   const int grid = ln_row_blocks(N, LN_FWD_MAX_GRID);
+#define LNF_ARGS                                                              \
+  (const short*)x, (const short*)res, (const short*)gamma,                    \
+      (const short*)beta, (short*)y, (short*)s_out, (float*)mean,             \
+      (float*)rstd, N, D, eps, dr
 #define LNF_T(P)                                                              \
   do {                                                                        \
-    if (res)                                                                  \
-      ln_fwd_t<P, true><<<grid, BLOCK, 0, stream>>>(                          \
-          (const short*)x, (const short*)res, (const short*)gamma,            \
-          (const short*)beta, (short*)y, (short*)s_out, (float*)mean,         \
-          (float*)rstd, N, D, eps);                                           \
-    else                                                                      \
-      ln_fwd_t<P, false><<<grid, BLOCK, 0, stream>>>(                         \
-          (const short*)x, nullptr, (const short*)gamma, (const short*)beta,  \
-          (short*)y, (short*)s_out, (float*)mean, (float*)rstd, N, D, eps);   \
+    if (res) {                                                                \
+      ln_fwd_t<P, true, DROP><<<grid, BLOCK, 0, stream>>>(LNF_ARGS);          \
+    } else if constexpr (!DROP) {                                             \
+      ln_fwd_t<P, false, false><<<grid, BLOCK, 0, stream>>>(LNF_ARGS);        \
+    }                                                                         \
   } while (0)
   if (D == 512) LNF_T(1);
   else if (D == 1024) LNF_T(2);
@@ -704,15 +802,14 @@ hipError_t ln_fwd_launch(const void* x, const void* res, const void* gamma,
   // PKTS=8 (D=4096) allocates 256 VGPRs (1 wave/SIMD) — the general kernel
   // is the better trade there
   else
-    ln_fwd_kernel<<<grid, BLOCK, 0, stream>>>(
-        (const short*)x, (const short*)res, (const short*)gamma,
-        (const short*)beta, (short*)y, (short*)s_out, (float*)mean,
-        (float*)rstd, N, D, eps);
+    ln_fwd_kernel<DROP><<<grid, BLOCK, 0, stream>>>(LNF_ARGS);
 #undef LNF_T
+#undef LNF_ARGS
   return hipGetLastError();
 }
 
 // runtime A/B: TOSEM_LN_BWD=1row selects the single-row ln_bwd_t variant
+// (no dropout instantiation: the dropout launcher always runs ln_bwd_t2)
 static int ln_bwd_use_1row() {
   static int v = -1;
   if (v < 0) {
@@ -722,45 +819,68 @@ static int ln_bwd_use_1row() {
   return v;
 }
 
-// ws is [ln_bwd_ws_rows(N, D), n_out * D] f32 with n_out = 2
-// ([dgamma | dbeta]) or 3 (+ [dres_sum]); every width supports both.
-hipError_t ln_bwd_launch(const void* dy, const void* x, const void* gamma,
-                         const void* mean, const void* rstd,
-                         const void* ds_extra, void* dx, void* ws, int n_out,
-                         int N, int D, hipStream_t stream) {
-  if (n_out != 2 && n_out != 3) return hipErrorInvalidValue;
+// DROP: n_out is 2 and dres_out the [N, D] gradient of the dropped residual;
+// D <= LN_BWD_G_MAX_D.
+template <bool DROP>
+static hipError_t ln_bwd_dispatch(const void* dy, const void* x,
+                                  const void* gamma, const void* mean,
+                                  const void* rstd, const void* ds_extra,
+                                  void* dx, void* ws, int n_out, int N, int D,
+                                  void* dres_out, LnDrop dr,
+                                  hipStream_t stream) {
   const int grid = ln_bwd_grid(N, D);
   const bool dres = n_out == 3;
   size_t shm = (size_t)D * n_out * sizeof(float);
 #define LNB_ARGS                                                              \
   (const short*)dy, (const short*)x, (const short*)gamma, (const float*)mean, \
       (const float*)rstd, (const short*)ds_extra, (short*)dx, (float*)ws, N, D
-#define LNB_K(K, P)                                                           \
+#define LNB_DROP (short*)dres_out, dr
+#define LNB_T1(P)                                                             \
   do {                                                                        \
     if (ds_extra && dres) {                                                   \
-      K<P, true, true><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);                 \
+      ln_bwd_t<P, true, true><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);          \
     } else if (ds_extra) {                                                    \
-      K<P, true, false><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);                \
+      ln_bwd_t<P, true, false><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);         \
     } else if (dres) {                                                        \
-      K<P, false, true><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);                \
+      ln_bwd_t<P, false, true><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);         \
     } else {                                                                  \
-      K<P, false, false><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);               \
+      ln_bwd_t<P, false, false><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);        \
+    }                                                                         \
+  } while (0)
+#define LNB_T2(P)                                                             \
+  do {                                                                        \
+    if (!dres && ds_extra) {                                                  \
+      ln_bwd_t2<P, true, false, DROP><<<grid, BLOCK, 0, stream>>>(            \
+          LNB_ARGS, LNB_DROP);                                                \
+    } else if (!dres) {                                                       \
+      ln_bwd_t2<P, false, false, DROP><<<grid, BLOCK, 0, stream>>>(           \
+          LNB_ARGS, LNB_DROP);                                                \
+    } else if constexpr (!DROP) {                                             \
+      if (ds_extra) {                                                         \
+        ln_bwd_t2<P, true, true, false><<<grid, BLOCK, 0, stream>>>(          \
+            LNB_ARGS, LNB_DROP);                                              \
+      } else {                                                                \
+        ln_bwd_t2<P, false, true, false><<<grid, BLOCK, 0, stream>>>(         \
+            LNB_ARGS, LNB_DROP);                                              \
+      }                                                                       \
     }                                                                         \
   } while (0)
 #define LNB_T(P)                                                              \
   do {                                                                        \
-    if (ln_bwd_use_1row()) {                                                  \
-      LNB_K(ln_bwd_t, P);                                                     \
+    if (!DROP && ln_bwd_use_1row()) {                                         \
+      LNB_T1(P);                                                              \
     } else {                                                                  \
-      LNB_K(ln_bwd_t2, P);                                                    \
+      LNB_T2(P);                                                              \
     }                                                                         \
   } while (0)
 #define LNB_G(P)                                                              \
   do {                                                                        \
-    if (dres) {                                                               \
-      ln_bwd_g<P, true><<<grid, BLOCK, shm, stream>>>(LNB_ARGS);              \
-    } else {                                                                  \
-      ln_bwd_g<P, false><<<grid, BLOCK, shm, stream>>>(LNB_ARGS);             \
+    if (!dres) {                                                              \
+      ln_bwd_g<P, false, DROP><<<grid, BLOCK, shm, stream>>>(LNB_ARGS,        \
+                                                             LNB_DROP);       \
+    } else if constexpr (!DROP) {                                             \
+      ln_bwd_g<P, true, false><<<grid, BLOCK, shm, stream>>>(LNB_ARGS,        \
+                                                             LNB_DROP);       \
     }                                                                         \
   } while (0)
   if (D == 512) LNB_T(1);
@@ -769,24 +889,89 @@ hipError_t ln_bwd_launch(const void* dy, const void* x, const void* gamma,
   else if (D <= 1024) LNB_G(2);
   else if (D <= 2048) LNB_G(4);
   else if (D <= LN_BWD_G_MAX_D) LNB_G(8);
-  else if (dres) {
-    ln_bwd_wide_kernel<true><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);
-  } else {
-    ln_bwd_wide_kernel<false><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);
+  else if constexpr (!DROP) {
+    if (dres) {
+      ln_bwd_wide_kernel<true><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);
+    } else {
+      ln_bwd_wide_kernel<false><<<grid, BLOCK, 0, stream>>>(LNB_ARGS);
+    }
   }
 #undef LNB_G
 #undef LNB_T
-#undef LNB_K
+#undef LNB_T2
+#undef LNB_T1
+#undef LNB_DROP
 #undef LNB_ARGS
   return hipGetLastError();
 }
 
-// Workspace rows ln_bwd_launch writes: one per block (the waves merge through
-// LDS), one per wave on the wide path.  Either way the column sum reduces
-// them in fixed order.
+// thr in [1, 65535]; the scale is formed in double and rounded once, like
+// reference.dropout_threshold's
+static bool ln_drop_args(unsigned long long seed, unsigned call, unsigned site,
+                         unsigned thr, LnDrop* dr) {
+  if (thr < 1 || thr > 65535) return false;
+  *dr = LnDrop{(unsigned)seed, (unsigned)(seed >> 32), call, site, thr,
+               (float)(65536.0 / (double)(65536 - thr))};
+  return true;
+}
+
+extern "C" {
+
+hipError_t ln_fwd_launch(const void* x, const void* res, const void* gamma,
+                         const void* beta, void* y, void* s_out, void* mean,
+                         void* rstd, int N, int D, float eps,
+                         hipStream_t stream) {
+  return ln_fwd_dispatch<false>(x, res, gamma, beta, y, s_out, mean, rstd, N,
+                                D, eps, LnDrop{}, stream);
+}
+
+hipError_t ln_drop_fwd_launch(const void* x, const void* res,
+                              const void* gamma, const void* beta, void* y,
+                              void* s_out, void* mean, void* rstd, int N,
+                              int D, float eps, unsigned long long seed,
+                              unsigned call, unsigned site, unsigned thr,
+                              hipStream_t stream) {
+  LnDrop dr;
+  if (!res || !s_out || !ln_drop_args(seed, call, site, thr, &dr))
+    return hipErrorInvalidValue;
+  return ln_fwd_dispatch<true>(x, res, gamma, beta, y, s_out, mean, rstd, N,
+                               D, eps, dr, stream);
+}
+
+// ws is [ln_bwd_ws_rows(N, D), n_out * D] f32 with n_out = 2
+// ([dgamma | dbeta]) or 3 (+ [dres_sum]); every width supports both.
+hipError_t ln_bwd_launch(const void* dy, const void* x, const void* gamma,
+                         const void* mean, const void* rstd,
+                         const void* ds_extra, void* dx, void* ws, int n_out,
+                         int N, int D, hipStream_t stream) {
+  if (n_out != 2 && n_out != 3) return hipErrorInvalidValue;
+  return ln_bwd_dispatch<false>(dy, x, gamma, mean, rstd, ds_extra, dx, ws,
+                                n_out, N, D, nullptr, LnDrop{}, stream);
+}
+
+hipError_t ln_drop_bwd_launch(const void* dy, const void* x,
+                              const void* gamma, const void* mean,
+                              const void* rstd, const void* ds_extra, void* dx,
+                              void* dres, void* ws, int N, int D,
+                              unsigned long long seed, unsigned call,
+                              unsigned site, unsigned thr,
+                              hipStream_t stream) {
+  LnDrop dr;
+  if (!dres || D > LN_BWD_G_MAX_D || !ln_drop_args(seed, call, site, thr, &dr))
+    return hipErrorInvalidValue;
+  return ln_bwd_dispatch<true>(dy, x, gamma, mean, rstd, ds_extra, dx, ws, 2,
+                               N, D, dres, dr, stream);
+}
+
+int ln_drop_bwd_max_d(void) { return LN_BWD_G_MAX_D; }
+
+// Workspace rows ln_bwd_launch and ln_drop_bwd_launch write: one per block
+// (the waves merge through LDS), one per wave on the wide path.  Either way
+// the column sum reduces them in fixed order.
 int ln_bwd_ws_rows(int N, int D) {
   const int grid = ln_bwd_grid(N, D);
   return D > LN_BWD_G_MAX_D ? grid * WAVES_PER_BLOCK : grid;
 }
 
 }  // extern "C"
+

@@ -262,6 +262,88 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
   return out;
 }
 
+// The mask's words as the launchers take them (csrc/philox.h).
+void check_drop_args(int64_t call, int64_t site, int64_t thr) {
+  TORCH_CHECK(call >= 0 && call <= 0xffffffffLL, "call must fit 32 bits");
+  TORCH_CHECK(site >= 0 && site <= 0xffffffffLL, "site must fit 32 bits");
+  TORCH_CHECK(thr >= 1 && thr <= 65535,
+              "dropout threshold must be in [1, 65535], got ", thr);
+}
+
+// layernorm_fwd with the residual dropped first:
+// s = bf16(x + (keep ? residual * scale : 0)), y = LN(s).  thr is
+// round(p * 65536); seed, call, site select the mask.
+std::vector<torch::Tensor> layernorm_drop_fwd(torch::Tensor x,
+                                              torch::Tensor residual,
+                                              torch::Tensor gamma,
+                                              torch::Tensor beta, double eps,
+                                              uint64_t seed, int64_t call,
+                                              int64_t site, int64_t thr) {
+  check_bf16(x, "x"); check_bf16(gamma, "gamma"); check_bf16(beta, "beta");
+  check_bf16(residual, "residual");
+  const int D = (int)x.size(-1);
+  const long N = x.numel() / D;
+  TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8, got ", D);
+  check_numel(gamma, "gamma", D, "[D]");
+  check_numel(beta, "beta", D, "[D]");
+  TORCH_CHECK(residual.sizes() == x.sizes(), "residual shape mismatch");
+  // the forward kernels take any width; refuse here what the backward
+  // cannot follow, before a training step is half done
+  TORCH_CHECK(D <= ln_drop_bwd_max_d(), "fused dropout LayerNorm supports "
+              "D <= ", ln_drop_bwd_max_d(), ", got ", D);
+  check_drop_args(call, site, thr);
+  auto y = torch::empty_like(x);
+  auto s_out = torch::empty_like(x);
+  auto opts = x.options().dtype(torch::kFloat32);
+  auto mean = torch::empty({N}, opts);
+  auto rstd = torch::empty({N}, opts);
+  CHECK_HIP(ln_drop_fwd_launch(x.data_ptr(), residual.data_ptr(),
+                               gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+                               s_out.data_ptr(), mean.data_ptr(),
+                               rstd.data_ptr(), (int)N, D, (float)eps, seed,
+                               (unsigned)call, (unsigned)site, (unsigned)thr,
+                               cur_stream()));
+  return {y, s_out, mean, rstd};
+}
+
+// Returns {dx, dres, dgamma, dbeta}: dx, dgamma and dbeta exactly as
+// layernorm_bwd's, dres the gradient of the dropped residual, its mask
+// regenerated from (seed, call, site, thr).
+std::vector<torch::Tensor> layernorm_drop_bwd(
+    torch::Tensor dy, torch::Tensor x, torch::Tensor gamma, torch::Tensor mean,
+    torch::Tensor rstd, c10::optional<torch::Tensor> ds_extra, bool out_bf16,
+    uint64_t seed, int64_t call, int64_t site, int64_t thr) {
+  check_bf16(dy, "dy"); check_bf16(x, "x"); check_bf16(gamma, "gamma");
+  const int D = (int)x.size(-1);
+  const long N = x.numel() / D;
+  TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8, got ", D);
+  TORCH_CHECK(D <= ln_drop_bwd_max_d(), "fused dropout LayerNorm backward "
+              "supports D <= ", ln_drop_bwd_max_d(), ", got ", D);
+  TORCH_CHECK(dy.numel() == x.numel(), "dy shape mismatch");
+  check_numel(gamma, "gamma", D, "[D]");
+  check_f32(mean, "mean"); check_f32(rstd, "rstd");
+  TORCH_CHECK(mean.numel() == N && rstd.numel() == N,
+              "mean and rstd must be [N]");
+  check_drop_args(call, site, thr);
+  const void* de = nullptr;
+  if (ds_extra.has_value()) {
+    check_bf16(*ds_extra, "ds_extra");
+    TORCH_CHECK(ds_extra->numel() == x.numel(), "ds_extra shape mismatch");
+    de = ds_extra->data_ptr();
+  }
+  auto dx = torch::empty_like(x);
+  auto dres = torch::empty_like(x);
+  auto ws = torch::empty({ln_bwd_ws_rows((int)N, D), 2 * D},
+                         x.options().dtype(torch::kFloat32));
+  CHECK_HIP(ln_drop_bwd_launch(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(),
+                               mean.data_ptr(), rstd.data_ptr(), de,
+                               dx.data_ptr(), dres.data_ptr(), ws.data_ptr(),
+                               (int)N, D, seed, (unsigned)call, (unsigned)site,
+                               (unsigned)thr, cur_stream()));
+  auto cols = colsum(ws, 2 * D, out_bf16);
+  return {dx, dres, cols.narrow(0, 0, D), cols.narrow(0, D, D)};
+}
+
 torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor b) {
   check_bf16(x, "x"); check_bf16(b, "b");
   const int D = (int)x.size(-1);
@@ -827,6 +909,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dy"), py::arg("x"), py::arg("gamma"), py::arg("mean"),
         py::arg("rstd"), py::arg("ds_extra"), py::arg("want_dres") = false,
         py::arg("out_bf16") = false);
+  m.def("layernorm_drop_fwd", &layernorm_drop_fwd,
+        "fused residual dropout + add + LayerNorm fwd",
+        py::arg("x"), py::arg("residual"), py::arg("gamma"), py::arg("beta"),
+        py::arg("eps"), py::arg("seed"), py::arg("call"), py::arg("site"),
+        py::arg("thr"));
+  m.def("layernorm_drop_bwd", &layernorm_drop_bwd,
+        "fused residual dropout + add + LayerNorm bwd",
+        py::arg("dy"), py::arg("x"), py::arg("gamma"), py::arg("mean"),
+        py::arg("rstd"), py::arg("ds_extra"), py::arg("out_bf16"),
+        py::arg("seed"), py::arg("call"), py::arg("site"), py::arg("thr"));
   m.def("bias_gelu_fwd", &bias_gelu_fwd, "fused bias+GeLU fwd");
   m.def("lt_linear_gelu_bias", &lt_linear_gelu_bias,
         "hipBLASLt GEMM with fused GELU_BIAS epilogue (inference)");

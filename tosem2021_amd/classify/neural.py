@@ -202,6 +202,7 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                      resume: bool = False, device: Optional[str] = None,
                      eval_every: int = 0, seed: int = 0,
                      dropout: float = 0.0,
+                     fused_dropout: bool = False,
                      pretrain_path: Optional[str] = None,
                      pretrain_steps: int = 0,
                      focal_gamma_property: float = 0.0,
@@ -212,6 +213,11 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                      pack: bool = False,
                      max_grad_norm: float = 0.0) -> dict:
     """Fine-tune MLTC on `taxonomy_path`'s labeled rows.
+
+    `fused_dropout` runs the residual dropout inside the add+LayerNorm
+    kernels with a counter-based mask seeded by `seed`
+    (MLTCConfig.fused_dropout): no mask tensors, and a resumed run draws the
+    masks an uninterrupted one would.
 
     `max_grad_norm` > 0 clips the global gradient norm and skips steps whose
     gradient is not finite (TrainConfig.max_grad_norm); the result then also
@@ -232,7 +238,8 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
         torch.device("cpu"))
     base = CONFIGS[model]
     cfg = MLTCConfig(**{**base.__dict__, "max_seq": seq,
-                     "dropout": dropout})
+                     "dropout": dropout, "fused_dropout": fused_dropout,
+                     "dropout_seed": seed})
     full = _load_dataset(taxonomy_path, cfg)
     # split_seed pins the train/val partition independently of the training
     # seed, so differently-seeded runs share one val set and their dumped

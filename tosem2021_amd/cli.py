@@ -138,6 +138,7 @@ def cmd_train(args):
         taxonomy_path=args.taxonomy, model=args.model, steps=args.steps,
         batch=args.batch, seq=args.seq, lr=args.lr, ckpt_dir=args.ckpt_dir,
         resume=args.resume, dropout=args.dropout,
+        fused_dropout=args.fused_dropout,
         pretrain_path=args.pretrain, pretrain_steps=args.pretrain_steps,
         focal_gamma_property=args.focal_gamma_property,
         label_smoothing=args.label_smoothing, eval_every=args.eval_every,
@@ -228,6 +229,9 @@ def main(argv=None):
     p.add_argument("--ckpt-dir", default=None)
     p.add_argument("--resume", action="store_true")
     p.add_argument("--dropout", type=float, default=0.0)
+    p.add_argument("--fused-dropout", action="store_true",
+                   help="residual dropout inside the add+LayerNorm kernels, "
+                        "counter-based mask (reproducible across resume)")
     p.add_argument("--pretrain", default=None,
                    help="mined taxonomy to pretrain on before fine-tuning")
     p.add_argument("--pretrain-steps", type=int, default=0)

@@ -50,6 +50,12 @@ class MLTCConfig:
     d_ff: int = 4096
     max_seq: int = 512
     dropout: float = 0.0
+    # fused_dropout: in training mode with dropout > 0 the residual dropout
+    # runs inside the add+LayerNorm kernels (ops.fused_dropout_add_layernorm)
+    # with a counter-based mask seeded by dropout_seed, instead of F.dropout
+    # and torch's global generator.  Another random stream, so a switch.
+    fused_dropout: bool = False
+    dropout_seed: int = 0
     layer_norm_eps: float = 1e-5
     heads: Dict[str, int] = field(default_factory=lambda: dict(HEAD_SIZES))
 
@@ -230,6 +236,11 @@ class EncoderBlock(nn.Module):
     goes to this block's ln2; the caller passes the previous block's
     ffn.down.bias in as delta_bias and hands this block's on to the next
     consumer of the returned delta (the next block's ln1, or ln_f).
+
+    With drop = (p, seed, call), the fused residual dropout of this forward,
+    the deltas travel un-dropped and each consuming add+LayerNorm drops its
+    delta itself: block i's ln2 at site 2i (its attention delta), and the
+    consumer of its ffn delta, the next block's ln1 or ln_f, at site 2i + 1.
     """
 
     def __init__(self, cfg: MLTCConfig):
@@ -249,7 +260,10 @@ class EncoderBlock(nn.Module):
         return not (self.dropout and self.training)
 
     def forward(self, x, delta, mask_bias, seg=None, delta_bias=None,
-                fold_bias: bool = False):
+                fold_bias: bool = False, drop=None, index: int = 0):
+        if drop is not None:
+            return self._forward_fused_dropout(x, delta, mask_bias, seg, drop,
+                                               index)
         if delta is None:
             y1 = ops.fused_layernorm(x, self.ln1.weight, self.ln1.bias,
                                      self.ln1.eps)
@@ -266,6 +280,21 @@ class EncoderBlock(nn.Module):
         h2 = self._drop(self.ffn(y2, fold_bias))
         return s2, h2
 
+    def _forward_fused_dropout(self, x, delta, mask_bias, seg, drop, index):
+        if delta is None:
+            y1 = ops.fused_layernorm(x, self.ln1.weight, self.ln1.bias,
+                                     self.ln1.eps)
+            s1 = x
+        else:
+            y1, s1 = ops.fused_dropout_add_layernorm(
+                x, delta, self.ln1.weight, self.ln1.bias, self.ln1.eps,
+                *drop, 2 * index - 1)
+        h = self.attn(y1, mask_bias, seg)
+        y2, s2 = ops.fused_dropout_add_layernorm(
+            s1, h, self.ln2.weight, self.ln2.bias, self.ln2.eps, *drop,
+            2 * index)
+        return s2, self.ffn(y2)
+
 
 class MLTC(nn.Module):
     def __init__(self, cfg: MLTCConfig,
@@ -277,6 +306,12 @@ class MLTC(nn.Module):
         super().__init__()
         self.cfg = cfg
         self.fold_bias_grad = fold_bias_grad
+        # fused dropout (cfg.fused_dropout): training-mode forwards so far,
+        # the `call` word of every mask, checkpointed by the Trainer so that
+        # a resumed run draws the masks an uninterrupted one would; and the
+        # data-parallel rank, so that ranks draw different masks
+        self.dropout_call = 0
+        self.dropout_rank = 0
         self.tok_emb = nn.Embedding(cfg.vocab_size, cfg.d_model)
         self.pos_emb = nn.Embedding(cfg.max_seq, cfg.d_model)
         self.blocks = nn.ModuleList(EncoderBlock(cfg) for _ in range(cfg.n_layers))
@@ -305,7 +340,28 @@ class MLTC(nn.Module):
                 and not (self.cfg.dropout and self.training)
                 and not _USE_FUSED_LINEAR and not _USE_WGRAD)
 
+    def _fused_dropout_args(self):
+        """(p, seed, call) of this forward's fused residual dropout, or None
+        where today's path runs: switch off, dropout 0, or eval mode."""
+        cfg = self.cfg
+        if not (cfg.fused_dropout and cfg.dropout and self.training):
+            return None
+        call = self.dropout_call
+        self.dropout_call += 1
+        return cfg.dropout, cfg.dropout_seed * 65536 + self.dropout_rank, call
+
     def _run_blocks(self, x, mask_bias, seg):
+        drop = self._fused_dropout_args()
+        if drop is not None:
+            delta = None
+            for i, blk in enumerate(self.blocks):
+                x, delta = blk(x, delta, mask_bias, seg, drop=drop, index=i)
+            if delta is None:
+                return self.ln_f(x)
+            x, _ = ops.fused_dropout_add_layernorm(
+                x, delta, self.ln_f.weight, self.ln_f.bias, self.ln_f.eps,
+                *drop, 2 * len(self.blocks) - 1)
+            return x
         fold = self._fold_active(x)
         delta = delta_bias = None
         for blk in self.blocks:

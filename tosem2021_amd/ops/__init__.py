@@ -127,6 +127,65 @@ def fused_add_layernorm(x, residual, gamma, beta, eps: float = 1e-5,
                                  gamma, beta, eps, residual_bias)
 
 
+class _DropoutAddLayerNormFn(torch.autograd.Function):
+    """(y, s) = (LN(s), x + dropout(residual)) with the dropout fused into
+    the LN kernel's read of `residual` and, in backward, into its write of
+    the residual's gradient.  The keep mask is a pure function of (seed,
+    call, site, element index) — reference.dropout_keep, csrc/philox.h — so
+    no mask tensor exists at any point: backward regenerates it from the
+    Python ints kept on ctx."""
+
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, eps, p, seed, call, site):
+        thr, scale = reference.dropout_threshold(p)
+        # the words the Philox key and counter hold
+        seed, call, site = (seed & 0xFFFFFFFFFFFFFFFF, call & 0xFFFFFFFF,
+                            site & 0xFFFFFFFF)
+        ctx.drop = (p, seed, call, site, thr, scale)
+        if x.is_cuda:
+            y, s, mean, rstd = hip_ops().layernorm_drop_fwd(
+                x, residual, gamma, beta, eps, seed, call, site, thr)
+        else:
+            keep = reference.dropout_keep(x.numel() // x.shape[-1],
+                                          x.shape[-1], p, seed, call, site)
+            y, s, mean, rstd = reference.add_layernorm_fwd(
+                x, residual * keep.view(x.shape) * scale, gamma, beta, eps)
+        ctx.save_for_backward(s, gamma, mean, rstd)
+        return y, s
+
+    @staticmethod
+    def backward(ctx, dy, ds):
+        s, gamma, mean, rstd = ctx.saved_tensors
+        p, seed, call, site, thr, scale = ctx.drop
+        dy = dy.contiguous()
+        if s.is_cuda:
+            de = ds.contiguous() if ds is not None else None
+            dx, dres, dgamma, dbeta = hip_ops().layernorm_drop_bwd(
+                dy, s, gamma, mean, rstd, de, True, seed, call, site, thr)
+            return dx, dres, dgamma, dbeta, None, None, None, None, None
+        dx, dgamma, dbeta = reference.layernorm_bwd(dy, s, gamma, mean, rstd)
+        if ds is not None:
+            dx = dx + ds
+        keep = reference.dropout_keep(s.numel() // s.shape[-1], s.shape[-1],
+                                      p, seed, call, site)
+        dres = dx * keep.view(s.shape) * scale
+        return (dx, dres, dgamma.to(gamma.dtype), dbeta.to(gamma.dtype),
+                None, None, None, None, None)
+
+
+def fused_dropout_add_layernorm(x, residual, gamma, beta, eps: float,
+                                p: float, seed: int, call: int, site: int):
+    """Returns (y, s): s = x + (keep ? residual * scale : 0) rounded to
+    x.dtype, y = LN(s).  keep and scale: reference.dropout_keep and
+    reference.dropout_threshold for probability p in (0, 1); p == 0 callers
+    use fused_add_layernorm.  (seed, call, site) select the mask: the same
+    ints give the same mask on the CPU and on the GPU, in forward and in
+    backward."""
+    reference.dropout_threshold(p)      # rejects p outside (0, 1)
+    return _DropoutAddLayerNormFn.apply(x.contiguous(), residual.contiguous(),
+                                        gamma, beta, eps, p, seed, call, site)
+
+
 class _BiasGeluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, b):

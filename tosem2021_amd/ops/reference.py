@@ -9,6 +9,7 @@ from __future__ import annotations
 import math
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 
@@ -59,6 +60,64 @@ def folded_bias_grad(g: torch.Tensor) -> torch.Tensor:
     of g over every dim but the last — what addmm's backward computes with
     sum(0), and what the HIP kernels that produce g emit alongside it."""
     return g.float().reshape(-1, g.shape[-1]).sum(dim=0)
+
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key) -> np.ndarray:
+    """Philox4x32-10 with the Random123 constants (csrc/philox.h holds the
+    same rounds for the kernels).  counter: four uint32 words, each a scalar
+    or an array (broadcast together); key: two uint32 scalars.  Returns
+    uint32 [..., 4].  uint64 NumPy arithmetic: a 32 x 32 product needs 64
+    bits, which torch's int64 would overflow."""
+    c0, c1, c2, c3 = np.broadcast_arrays(
+        *(np.asarray(w, dtype=np.uint64) for w in counter))
+    k0, k1 = (int(k) & _M32 for k in key)
+    m32 = np.uint64(_M32)
+    for _ in range(10):
+        p0 = np.uint64(_PHILOX_M0) * c0
+        p1 = np.uint64(_PHILOX_M1) * c2
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0),
+                          p1 & m32,
+                          (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1),
+                          p0 & m32)
+        k0 = (k0 + _PHILOX_W0) & _M32
+        k1 = (k1 + _PHILOX_W1) & _M32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def dropout_threshold(p: float) -> Tuple[int, float]:
+    """(thr, scale) of dropout probability p, 0 < p < 1: an element is
+    dropped iff its 16 random bits are below thr = round(p * 65536), clamped
+    to [1, 65535]; scale = 65536 / (65536 - thr) is the inverse of the
+    effective keep rate, so the expectation is exact."""
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"dropout probability must be in (0, 1), got {p}")
+    thr = min(max(int(math.floor(p * 65536 + 0.5)), 1), 65535)
+    return thr, 65536 / (65536 - thr)
+
+
+def dropout_keep(N: int, D: int, p: float, seed: int, call: int,
+                 site: int) -> torch.Tensor:
+    """Keep mask (bool [N, D], D % 8 == 0) of the fused residual dropout: a
+    pure function of (seed, call, site, element index).  One Philox call
+    covers the 8-element packet pkt = (row * D + col) / 8: counter =
+    (pkt lo, pkt hi, site, call), key = (seed lo, seed hi); output word w
+    gives element 2w from its low and element 2w+1 from its high 16 bits."""
+    if D % 8:
+        raise ValueError(f"D must be a multiple of 8, got {D}")
+    thr, _ = dropout_threshold(p)
+    pkt = np.arange(N * D // 8, dtype=np.uint64)
+    words = philox4x32_10(
+        (pkt & np.uint64(_M32), pkt >> np.uint64(32), site & _M32,
+         call & _M32),
+        (seed & _M32, (seed >> 32) & _M32))                     # [P, 4]
+    bits = np.stack([words & np.uint32(0xFFFF), words >> np.uint32(16)],
+                    axis=-1)                                    # [P, 4, 2]
+    return torch.from_numpy((bits >= thr).reshape(N, D))
 
 
 def bias_gelu_fwd(x: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -100,6 +100,8 @@ class Trainer:
             # rank-0 init everywhere: broadcast the flat params once
             dist.broadcast(self.flat.flat, src=0)
             self.flat.master.copy_(self.flat.flat.float())
+            # fused dropout: every rank draws its own masks
+            self.model.dropout_rank = dist.get_rank()
         self.step_num = 0     # attempted steps: LR schedule, checkpoint names
         self.opt_step = 0     # applied updates: AdamW's bias correction
         self.skipped_steps = 0
@@ -212,6 +214,9 @@ class Trainer:
             "step": self.step_num,
             "opt_step": self.opt_step,
             "skipped_steps": self.skipped_steps,
+            # the fused dropout's call counter: with it a resumed run draws
+            # the masks the uninterrupted run would have drawn
+            "dropout_call": self.model.dropout_call,
             "flat": self.flat.flat,
             "master": self.flat.master,
             "m": self.flat.m,
@@ -254,6 +259,7 @@ class Trainer:
         # checkpoints from before step skipping applied every step
         self.opt_step = sd.get("opt_step", sd["step"])
         self.skipped_steps = sd.get("skipped_steps", 0)
+        self.model.dropout_call = sd.get("dropout_call", 0)
 
     @staticmethod
     def latest_checkpoint(ckpt_dir: str) -> Optional[str]:
