@@ -6,8 +6,9 @@
 //   flash_bwd_fused_kernel     dK, dV (one wave per 32-row kv block)
 //   flash_dq_recompute_kernel  dQ, recomputing S/dP/dS in registers
 //   flash_dq_kernel            dQ = dS @ K from a materialized dS (A/B path)
-// plus fa_dot (D = rowsum(dO * O)).  The default backward is
-// fa_dot + flash_bwd_fused + flash_dq_recompute.
+// plus fa_dot (D = rowsum(dO * O), and one flag per 32-row query tile whose
+// dO is all +-0, which the two backward kernels then leave out).  The
+// default backward is fa_dot + flash_bwd_fused + flash_dq_recompute.
 //
 // Shared structure (guide §B "fused attention prefill" adapted):
 //  * swapped QK^T — compute mfma(A=K, B=Q^T) so the score column for one
@@ -350,6 +351,63 @@ __device__ __forceinline__ bool fa_seg_tile_live(const int (&r)[16], int a,
   return __builtin_amdgcn_ballot_w64(hit) != 0;
 }
 
+// ---- dead query tiles --------------------------------------------------------
+// dead is uint8 [B, H, L / 32] from fa_dot (nullptr = skip nothing): 1 marks
+// a 32-row query tile whose dO block is all +-0.  Such a tile adds exact
+// zeros to dK and dV and its own dQ rows are zero, so both backward kernels
+// leave it out.  The flags are data the previous kernel wrote, the same for
+// every wave of a workgroup, so every branch on them is workgroup-uniform.
+//
+// fa_live_window: bit i = tile (t0 + i) exists and is live, for the 64 tiles
+// from t0 — one byte load per lane and a ballot, so the result is scalar.
+__device__ __forceinline__ unsigned long long fa_live_window(
+    const unsigned char* dead_bh, int t0, int n_t, int lane) {
+  const int t = t0 + lane;
+  bool lv = t < n_t;
+  if (lv && dead_bh) lv = dead_bh[t] == 0;
+  return __builtin_amdgcn_ballot_w64(lv);
+}
+
+// Zero rows [q0, min(q0 + 32, L)) of a [*, 64]-column bf16 tile, rows rs
+// shorts apart: one wave, 16 B per lane, eight rows per store.
+__device__ __forceinline__ void fa_store_zero_tile(short* base, int rs, int q0,
+                                                   int L, int lane) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = q0 + 8 * i + (lane >> 3);
+    if (row < L)
+      *(short8_t*)(base + (long)row * rs + (lane & 7) * 8) = (short8_t)(0);
+  }
+}
+
+// Scalar scan over the windows: first live tile in [qt, n_q), or n_q.
+struct FaLiveScan {
+  const unsigned char* dead_bh;
+  int n_t, lane, win;
+  unsigned long long bits;
+  __device__ __forceinline__ FaLiveScan(const unsigned char* d, int n_t_,
+                                        int lane_)
+      : dead_bh(d), n_t(n_t_), lane(lane_), win(-1), bits(0) {}
+  // Window 0 up front, so the flag load is in flight with whatever the
+  // kernel loads first instead of ahead of its first tile.
+  __device__ __forceinline__ void preload() {
+    if (dead_bh) { win = 0; bits = fa_live_window(dead_bh, 0, n_t, lane); }
+  }
+  __device__ __forceinline__ int next(int qt, int n_q) {
+    if (!dead_bh) return qt;
+    while (qt < n_q) {
+      if ((qt >> 6) != win) {
+        win = qt >> 6;
+        bits = fa_live_window(dead_bh, win << 6, n_t, lane);
+      }
+      const unsigned long long m = bits >> (qt & 63);
+      if (m) return min(qt + (int)__builtin_ctzll(m), n_q);
+      qt = (win + 1) << 6;
+    }
+    return n_q;
+  }
+};
+
 template <bool SEG>
 __global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
@@ -665,6 +723,7 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
                        const int* __restrict__ seg,
                        const float* __restrict__ lse,
                        const float* __restrict__ ddot,
+                       const unsigned char* __restrict__ dead,
                        short* __restrict__ ds, short* __restrict__ dk,
                        short* __restrict__ dv,
                        int B, int H, int L, float scale, FaGeom g,
@@ -710,6 +769,13 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   // softmax-over-bias behavior.  skip is workgroup-uniform (the flag is a
   // barrier-ordered workgroup reduction), so branching around the
   // barriered q loop is safe.
+  // Dead query tiles (all-zero dO) are neither loaded nor staged: the q loop
+  // steps from live tile to live tile and the prefetch targets the next
+  // live one.  Never with ds: the A/B path must write every dS tile.
+  FaLiveScan live(ds == nullptr && dead ? dead + (long)bh * (L / 32) : nullptr,
+                  L / 32, lane);
+  live.preload();
+
   bool skip_tile = false;
   bool wave_skip = false;
   if (mrow && ds == nullptr) {
@@ -757,9 +823,13 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
     n_q = qr.hi / 32 + 1;
   }
   const FaStager st(tid);
-  short8_t qv8 = st.load(q + qkv_off, qt_begin * 32, g.qkv_rs);
-  short8_t dv8 = st.load(dout + o_off, qt_begin * 32, g.o_rs);
-  for (int qt = qt_begin; qt < n_q; ++qt) {
+  int qt = live.next(qt_begin, n_q), qt_next;
+  short8_t qv8, dv8;
+  if (qt < n_q) {
+    qv8 = st.load(q + qkv_off, qt * 32, g.qkv_rs);
+    dv8 = st.load(dout + o_off, qt * 32, g.o_rs);
+  }
+  for (; qt < n_q; qt = qt_next) {
     const int q0 = qt * 32;
     __syncthreads();
     st.store(q_lds, qv8);
@@ -770,9 +840,10 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
       if constexpr (SEG) seg_lds[tid] = srow[q0 + tid];
     }
     __syncthreads();
-    if (qt + 1 < n_q) {
-      qv8 = st.load(q + qkv_off, q0 + 32, g.qkv_rs);
-      dv8 = st.load(dout + o_off, q0 + 32, g.o_rs);
+    qt_next = live.next(qt + 1, n_q);
+    if (qt_next < n_q) {
+      qv8 = st.load(q + qkv_off, qt_next * 32, g.qkv_rs);
+      dv8 = st.load(dout + o_off, qt_next * 32, g.o_rs);
     }
 
     if (wave_skip) continue;
@@ -887,7 +958,8 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
 static void fa_bwd_fused_dispatch(const short* q, const short* k,
                                   const short* v, const void* dout,
                                   const void* mask, const void* seg,
-                                  const void* lse, const void* ddot, void* ds,
+                                  const void* lse, const void* ddot,
+                                  const void* dead, void* ds,
                                   short* dk, short* dv, int B, int H, int L,
                                   float scale, FaGeom g, float* bias_ws,
                                   hipStream_t stream) {
@@ -895,11 +967,12 @@ static void fa_bwd_fused_dispatch(const short* q, const short* k,
   const int bias_ld = 3 * H * FA_DH;
 #define FA_BWD_SEG_ARGS                                                       \
   q, k, v, (const short*)dout, nullptr, (const int*)seg, (const float*)lse,   \
-      (const float*)ddot, nullptr, dk, dv, B, H, L, scale, g, bias_ws, bias_ld
+      (const float*)ddot, (const unsigned char*)dead, nullptr, dk, dv, B, H,  \
+      L, scale, g, bias_ws, bias_ld
 #define FA_BWD_ARGS                                                           \
   q, k, v, (const short*)dout, (const float*)mask, nullptr,                   \
-      (const float*)lse, (const float*)ddot, (short*)ds, dk, dv, B, H, L,     \
-      scale, g, bias_ws, bias_ld
+      (const float*)lse, (const float*)ddot, (const unsigned char*)dead,      \
+      (short*)ds, dk, dv, B, H, L, scale, g, bias_ws, bias_ld
   if (seg && bias_ws) {
     flash_bwd_fused_kernel<true, true><<<grid, FA_BLOCK, BWD_SEG_LDS_BYTES,
                                          stream>>>(FA_BWD_SEG_ARGS);
@@ -917,15 +990,16 @@ static void fa_bwd_fused_dispatch(const short* q, const short* k,
 #undef FA_BWD_SEG_ARGS
 }
 
-// seg excludes the dS output: with seg given, ds must be nullptr
+// seg excludes the dS output: with seg given, ds must be nullptr.  dead is
+// ignored when ds is given.
 extern "C" hipError_t flash_bwd_fused_launch(
     const void* q, const void* k, const void* v, const void* dout,
     const void* mask, const void* seg, const void* lse, const void* ddot,
-    void* ds, void* dk, void* dv, int B, int H, int L, float scale,
-    hipStream_t stream) {
+    const void* dead, void* ds, void* dk, void* dv, int B, int H, int L,
+    float scale, hipStream_t stream) {
   if (seg && ds) return hipErrorInvalidValue;
   fa_bwd_fused_dispatch((const short*)q, (const short*)k, (const short*)v,
-                        dout, mask, seg, lse, ddot, ds, (short*)dk,
+                        dout, mask, seg, lse, ddot, dead, ds, (short*)dk,
                         (short*)dv, B, H, L, scale, FaGeom::bhld(H, L),
                         nullptr, stream);
   return hipGetLastError();
@@ -936,12 +1010,12 @@ extern "C" hipError_t flash_bwd_fused_launch(
 // k and v thirds are written here.
 extern "C" hipError_t flash_bwd_fused_packed_launch(
     const void* qkv, const void* dout, const void* mask, const void* seg,
-    const void* lse, const void* ddot, void* dqkv, void* bias_ws, int B,
-    int H, int L, float scale, hipStream_t stream) {
+    const void* lse, const void* ddot, const void* dead, void* dqkv,
+    void* bias_ws, int B, int H, int L, float scale, hipStream_t stream) {
   const int D = H * FA_DH;
   fa_bwd_fused_dispatch((const short*)qkv, (const short*)qkv + D,
                         (const short*)qkv + 2 * D, dout, mask, seg, lse, ddot,
-                        nullptr, (short*)dqkv + D, (short*)dqkv + 2 * D, B, H,
+                        dead, nullptr, (short*)dqkv + D, (short*)dqkv + 2 * D, B, H,
                         L, scale, FaGeom::packed(H, L), (float*)bias_ws,
                         stream);
   return hipGetLastError();
@@ -1064,6 +1138,7 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
                           const int* __restrict__ seg,
                           const float* __restrict__ lse,
                           const float* __restrict__ ddot,
+                          const unsigned char* __restrict__ dead,
                           short* __restrict__ dq,
                           int B, int H, int L, float scale, FaGeom g,
                           float* __restrict__ bias_ws, int bias_ld) {
@@ -1084,6 +1159,18 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   const int h = qb.bh % H;
   const long qkv_off = (long)b * g.qkv_bs + (long)h * g.qkv_hs;
   const long o_off = (long)b * g.o_bs + (long)h * g.o_hs;
+
+  // Dead query tiles (all-zero dO, see above): lanes 0..7 fetch the
+  // flags of the workgroup's eight tiles; a tile past L counts as dead.  The
+  // byte is loaded first and looked at only after the q/dO loads below are
+  // issued, so its latency is not ahead of theirs.
+  bool tile_dead = false;
+  if (dead) {
+    const int n_t = L / FA_QB;
+    const int t = (qb.qA - wid * FA_QB) / FA_QB + lane;
+    tile_dead = lane < 8 && (t >= n_t || dead[(long)qb.bh * n_t + t] != 0);
+  }
+
   const int my_qA = qb.qA + col;
   const int my_qB = qb.qB + col;
   const bool validA = my_qA < L;
@@ -1114,6 +1201,30 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   const float lseB = lse[(long)qb.bh * L + (validB ? my_qB : L - 1)];
   const float ddA = ddot[(long)qb.bh * L + (validA ? my_qA : L - 1)];
   const float ddB = ddot[(long)qb.bh * L + (validB ? my_qB : L - 1)];
+
+  // bit i of dmask = tile i dead; wave wid owns bits wid (block A) and
+  // 4 + wid (block B).  A dead tile's dQ rows are exact zeros.
+  const unsigned dmask = (unsigned)__builtin_amdgcn_ballot_w64(tile_dead);
+  // All eight dead: zero rows (and zero q-third bias partials), no K/V load.
+  // dmask is workgroup-uniform, so leaving before the barriers is safe.
+  if (dmask == 0xffu) {
+    fa_store_zero_tile(dq + qkv_off, g.qkv_rs, qb.qA, L, lane);
+    fa_store_zero_tile(dq + qkv_off, g.qkv_rs, qb.qB, L, lane);
+    if constexpr (BIAS) {
+      if (tid < 2 * FA_DH) {
+        const int n128 = (L + FA_QWG - 1) / FA_QWG;
+        const int blk = (qb.qA - wid * FA_QB) / FA_QWG + tid / FA_DH;
+        if (blk < n128)
+          bias_ws[((long)b * n128 + blk) * bias_ld + h * FA_DH + tid % FA_DH] =
+              0.f;
+      }
+    }
+    return;
+  }
+  // Both blocks of this wave dead: it keeps staging and keeps the barriers,
+  // skips the MFMA and softmax work, and its zero accumulators are stored by
+  // the common epilogue.
+  const bool wave_dead = ((dmask >> wid) & 0x11u) == 0x11u;
 
   f32x16 dqA[2], dqB[2];
 #pragma unroll
@@ -1146,6 +1257,7 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
       kv8 = st.load(k + qkv_off, kv0 + FA_KVB, g.qkv_rs);
       vv8 = st.load(v + qkv_off, kv0 + FA_KVB, g.qkv_rs);
     }
+    if (wave_dead) continue;
 
     float mb_r[16];
     int sk_r[16];
@@ -1260,18 +1372,20 @@ static void fa_dq_recompute_dispatch(const short* q, const short* k,
                                      const short* v, const void* dout,
                                      const void* mask, const void* seg,
                                      const void* lse, const void* ddot,
-                                     void* dq, int B, int H, int L,
-                                     float scale, FaGeom g, float* bias_ws,
+                                     const void* dead, void* dq, int B, int H,
+                                     int L, float scale, FaGeom g,
+                                     float* bias_ws,
                                      hipStream_t stream) {
   const dim3 grid = fa_grid(B, H, L, FA_Q2WG);
   const int bias_ld = 3 * H * FA_DH;
 #define FA_DQR_SEG_ARGS                                                       \
   q, k, v, (const short*)dout, nullptr, (const int*)seg, (const float*)lse,   \
-      (const float*)ddot, (short*)dq, B, H, L, scale, g, bias_ws, bias_ld
+      (const float*)ddot, (const unsigned char*)dead, (short*)dq, B, H, L,    \
+      scale, g, bias_ws, bias_ld
 #define FA_DQR_ARGS                                                           \
   q, k, v, (const short*)dout, (const float*)mask, nullptr,                   \
-      (const float*)lse, (const float*)ddot, (short*)dq, B, H, L, scale, g,   \
-      bias_ws, bias_ld
+      (const float*)lse, (const float*)ddot, (const unsigned char*)dead,      \
+      (short*)dq, B, H, L, scale, g, bias_ws, bias_ld
   if (seg && bias_ws) {
     flash_dq_recompute_kernel<true, true><<<grid, FA_BLOCK, DQR_LDS_BYTES,
                                             stream>>>(FA_DQR_SEG_ARGS);
@@ -1292,9 +1406,10 @@ static void fa_dq_recompute_dispatch(const short* q, const short* k,
 extern "C" hipError_t flash_dq_recompute_launch(
     const void* q, const void* k, const void* v, const void* dout,
     const void* mask, const void* seg, const void* lse, const void* ddot,
-    void* dq, int B, int H, int L, float scale, hipStream_t stream) {
+    const void* dead, void* dq, int B, int H, int L, float scale,
+    hipStream_t stream) {
   fa_dq_recompute_dispatch((const short*)q, (const short*)k, (const short*)v,
-                           dout, mask, seg, lse, ddot, dq, B, H, L, scale,
+                           dout, mask, seg, lse, ddot, dead, dq, B, H, L, scale,
                            FaGeom::bhld(H, L), nullptr, stream);
   return hipGetLastError();
 }
@@ -1303,22 +1418,30 @@ extern "C" hipError_t flash_dq_recompute_launch(
 // in flash_bwd_fused_packed_launch, the q third is written here.
 extern "C" hipError_t flash_dq_recompute_packed_launch(
     const void* qkv, const void* dout, const void* mask, const void* seg,
-    const void* lse, const void* ddot, void* dqkv, void* bias_ws, int B,
-    int H, int L, float scale, hipStream_t stream) {
+    const void* lse, const void* ddot, const void* dead, void* dqkv,
+    void* bias_ws, int B, int H, int L, float scale, hipStream_t stream) {
   const int D = H * FA_DH;
   fa_dq_recompute_dispatch((const short*)qkv, (const short*)qkv + D,
                            (const short*)qkv + 2 * D, dout, mask, seg, lse,
-                           ddot, dqkv, B, H, L, scale, FaGeom::packed(H, L),
+                           ddot, dead, dqkv, B, H, L, scale,
+                           FaGeom::packed(H, L),
                            (float*)bias_ws, stream);
   return hipGetLastError();
 }
 
-// D = rowsum(dO * O) over one 64-element (b, h, q) row: 16 lanes x 4 bf16,
-// reduced across the 16-lane group.  Every lane of the group gets the sum.
-__device__ __forceinline__ float fa_row_dot(const short* dr, const short* orow,
-                                            int sub) {
-  short4_t a = *(const short4_t*)(dr + sub * 4);
-  short4_t c = *(const short4_t*)(orow + sub * 4);
+// D = rowsum(dO * O) and the dead-tile flags, from one read of dO.
+//
+// One wave owns one 32-row query tile of one (b, h): eight passes of four
+// rows, 16 lanes x 4 bf16 per 64-element row, each row's dot product reduced
+// across its 16-lane group in a fixed order.  All sixteen loads of a lane
+// are issued before the first is used.
+//
+// dead[tile] = 1 iff every one of the tile's 32 x 64 dO elements is +-0
+// ((bits & 0x7fff) == 0), else 0: a plain store by lane 0 on every call, so
+// no memset and no state between calls.  For such a tile dP, D and dS are
+// exact zeros whatever P is (finite inputs), which is what lets the two
+// backward kernels skip it — see docs/KERNELS.md.
+__device__ __forceinline__ float fa_row_dot(short4_t a, short4_t c) {
   float s = 0.f;
 #pragma unroll
   for (int j = 0; j < 4; ++j) s += bf16_to_f32(a[j]) * bf16_to_f32(c[j]);
@@ -1327,52 +1450,90 @@ __device__ __forceinline__ float fa_row_dot(const short* dr, const short* orow,
   return s;
 }
 
-// dout/o [n_rows, 64] (any [B, H, L, 64]); ddot [n_rows].
-extern "C" __global__ void __launch_bounds__(256)
-fa_dot_kernel(const short* __restrict__ dout, const short* __restrict__ o,
-              float* __restrict__ ddot, long n_rows) {
-  long row = ((long)blockIdx.x * 256 + threadIdx.x) >> 4;
-  if (row >= n_rows) return;
-  int sub = threadIdx.x & 15;
-  float s = fa_row_dot(dout + row * FA_DH, o + row * FA_DH, sub);
-  if (sub == 0) ddot[row] = s;
+// dr/orow: row 0 of the tile, rows `rs` shorts apart; dd: the tile's 32 ddot
+// slots; n_valid: rows of the tile that exist (32 unless the tile is the
+// partial last one of a flat [n_rows, 64] tensor).
+__device__ __forceinline__ void fa_dot_tile(const short* dr, const short* orow,
+                                            long rs, float* dd,
+                                            unsigned char* dead_flag,
+                                            int n_valid, int lane) {
+  const int sub = lane & 15, grp = lane >> 4;
+  short4_t a[8], c[8];
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    const int r = min(4 * p + grp, n_valid - 1);
+    a[p] = *(const short4_t*)(dr + r * rs + sub * 4);
+    c[p] = *(const short4_t*)(orow + r * rs + sub * 4);
+  }
+  unsigned nz = 0;
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    const int r = 4 * p + grp;
+    const float s = fa_row_dot(a[p], c[p]);
+    if (r < n_valid) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) nz |= (unsigned)a[p][j] & 0x7fffu;
+      if (sub == 0) dd[r] = s;
+    }
+  }
+  const bool live = __builtin_amdgcn_ballot_w64(nz != 0) != 0;
+  if (lane == 0) *dead_flag = live ? 0 : 1;
 }
 
-// packed fa_dot: dout/o are [B, L, D] (D = H*64); ddot is [B, H, L].
-extern "C" __global__ void __launch_bounds__(256)
+// dout/o [n_rows, 64] (any [B, H, L, 64]); ddot [n_rows]; dead
+// [ceil(n_rows / 32)], = [B, H, L / 32] when L % 32 == 0.
+extern "C" __global__ void __launch_bounds__(FA_BLOCK)
+fa_dot_kernel(const short* __restrict__ dout, const short* __restrict__ o,
+              float* __restrict__ ddot, unsigned char* __restrict__ dead,
+              long n_rows) {
+  const long tile = (long)blockIdx.x * FA_WAVES + threadIdx.x / WAVE;
+  const long row0 = tile * FA_QB;
+  if (row0 >= n_rows) return;                       // wave-uniform
+  fa_dot_tile(dout + row0 * FA_DH, o + row0 * FA_DH, FA_DH, ddot + row0,
+              dead + tile, (int)min((long)FA_QB, n_rows - row0),
+              threadIdx.x & (WAVE - 1));
+}
+
+// packed fa_dot: dout/o are [B, L, D] (D = H*64); ddot is [B, H, L], dead
+// [B, H, L / 32].  Wave -> (b, tile, h), h fastest, so the waves of a
+// workgroup read neighbouring 128-B pieces of the same rows.
+extern "C" __global__ void __launch_bounds__(FA_BLOCK)
 fa_dot_packed_kernel(const short* __restrict__ dout,
                      const short* __restrict__ o, float* __restrict__ ddot,
-                     int B, int H, int L) {
+                     unsigned char* __restrict__ dead, int B, int H, int L) {
   const int D = H * FA_DH;
-  long n_rows = (long)B * L * H;          // one 64-elem chunk per (b, l, h)
-  long chunk = ((long)blockIdx.x * 256 + threadIdx.x) >> 4;
-  if (chunk >= n_rows) return;
-  int sub = threadIdx.x & 15;
-  int h = (int)(chunk % H);
-  long bl = chunk / H;                     // b * L + l
-  int l = (int)(bl % L);
-  int b = (int)(bl / L);
-  float s = fa_row_dot(dout + bl * D + h * FA_DH, o + bl * D + h * FA_DH, sub);
-  if (sub == 0) ddot[((long)b * H + h) * L + l] = s;
+  const int n_t = L / FA_QB;
+  const long wv = (long)blockIdx.x * FA_WAVES + threadIdx.x / WAVE;
+  if (wv >= (long)B * n_t * H) return;              // wave-uniform
+  const int h = (int)(wv % H);
+  const long bt = wv / H;                           // b * n_t + tile
+  const int t = (int)(bt % n_t);
+  const long b = bt / n_t;
+  const long in_off = (b * L + (long)t * FA_QB) * D + h * FA_DH;
+  const long bh = b * H + h;
+  fa_dot_tile(dout + in_off, o + in_off, D, ddot + bh * L + t * FA_QB,
+              dead + bh * n_t + t, FA_QB, threadIdx.x & (WAVE - 1));
 }
 
 extern "C" hipError_t fa_dot_packed_launch(const void* dout, const void* o,
-                                           void* ddot, int B, int H, int L,
-                                           hipStream_t stream) {
-  long total_threads = (long)B * H * L * 16;
-  int grid = (int)((total_threads + 255) / 256);
-  fa_dot_packed_kernel<<<grid, 256, 0, stream>>>(
-      (const short*)dout, (const short*)o, (float*)ddot, B, H, L);
+                                           void* ddot, void* dead, int B,
+                                           int H, int L, hipStream_t stream) {
+  const long waves = (long)B * H * (L / FA_QB);
+  const int grid = (int)((waves + FA_WAVES - 1) / FA_WAVES);
+  fa_dot_packed_kernel<<<grid, FA_BLOCK, 0, stream>>>(
+      (const short*)dout, (const short*)o, (float*)ddot, (unsigned char*)dead,
+      B, H, L);
   return hipGetLastError();
 }
 
 extern "C" hipError_t fa_dot_launch(const void* dout, const void* o,
-                                    void* ddot, long n_rows,
+                                    void* ddot, void* dead, long n_rows,
                                     hipStream_t stream) {
-  long total_threads = n_rows * 16;
-  int grid = (int)((total_threads + 255) / 256);
-  fa_dot_kernel<<<grid, 256, 0, stream>>>((const short*)dout, (const short*)o,
-                                          (float*)ddot, n_rows);
+  const long waves = (n_rows + FA_QB - 1) / FA_QB;
+  const int grid = (int)((waves + FA_WAVES - 1) / FA_WAVES);
+  fa_dot_kernel<<<grid, FA_BLOCK, 0, stream>>>(
+      (const short*)dout, (const short*)o, (float*)ddot, (unsigned char*)dead,
+      n_rows);
   return hipGetLastError();
 }
 

@@ -130,42 +130,49 @@ hipError_t flash_fwd_packed_launch(const void* qkv, const void* mask,
                                    const void* seg, void* o, void* lse, int B,
                                    int H, int L, float scale,
                                    hipStream_t stream);
-// ds (nullptr = none) [B, H, L, L] bf16; not together with seg.
+// dead (nullptr = skip nothing) uint8 [B, H, L / 32], as fa_dot writes it:
+// the backward kernels leave out the query tiles it marks, whose dO is all
+// +-0 and whose contribution is exact zeros.
+// ds (nullptr = none) [B, H, L, L] bf16; not together with seg, and with ds
+// given dead is ignored (every dS tile is written).
 hipError_t flash_bwd_fused_launch(const void* q, const void* k, const void* v,
                                   const void* dout, const void* mask,
                                   const void* seg, const void* lse,
-                                  const void* ddot, void* ds, void* dk,
-                                  void* dv, int B, int H, int L, float scale,
-                                  hipStream_t stream);
+                                  const void* ddot, const void* dead,
+                                  void* ds, void* dk, void* dv, int B, int H,
+                                  int L, float scale, hipStream_t stream);
 // bias_ws (nullptr = none) is [flash_bias_ws_rows(B, L), 3 * H * 64] f32; the
 // fused launcher fills its k and v thirds, the dq launcher its q third.
 hipError_t flash_bwd_fused_packed_launch(const void* qkv, const void* dout,
                                          const void* mask, const void* seg,
                                          const void* lse, const void* ddot,
-                                         void* dqkv, void* bias_ws, int B,
-                                         int H, int L, float scale,
-                                         hipStream_t stream);
+                                         const void* dead, void* dqkv,
+                                         void* bias_ws, int B, int H, int L,
+                                         float scale, hipStream_t stream);
 hipError_t flash_dq_recompute_packed_launch(const void* qkv, const void* dout,
                                             const void* mask, const void* seg,
                                             const void* lse, const void* ddot,
-                                            void* dqkv, void* bias_ws, int B,
-                                            int H, int L, float scale,
-                                            hipStream_t stream);
+                                            const void* dead, void* dqkv,
+                                            void* bias_ws, int B, int H, int L,
+                                            float scale, hipStream_t stream);
 int flash_bias_ws_rows(int B, int L);
 hipError_t flash_dq_recompute_launch(const void* q, const void* k,
                                      const void* v, const void* dout,
                                      const void* mask, const void* seg,
                                      const void* lse, const void* ddot,
-                                     void* dq, int B, int H, int L,
-                                     float scale, hipStream_t stream);
+                                     const void* dead, void* dq, int B, int H,
+                                     int L, float scale, hipStream_t stream);
 // ds [B, H, L, L] bf16.
 hipError_t flash_dq_launch(const void* ds, const void* k, void* dq, int B,
                            int H, int L, hipStream_t stream);
-// ddot [n_rows] f32 = rowsum(dout * o) over rows of 64.
+// ddot [n_rows] f32 = rowsum(dout * o) over rows of 64; dead uint8
+// [ceil(n_rows / 32)] (packed: [B, H, L / 32]) = 1 where all 32 x 64 dout
+// elements of the tile are +-0, else 0.  Every element of both is written.
 hipError_t fa_dot_launch(const void* dout, const void* o, void* ddot,
-                         long n_rows, hipStream_t stream);
+                         void* dead, long n_rows, hipStream_t stream);
 hipError_t fa_dot_packed_launch(const void* dout, const void* o, void* ddot,
-                                int B, int H, int L, hipStream_t stream);
+                                void* dead, int B, int H, int L,
+                                hipStream_t stream);
 // src [256] bf16 -> out [64, 4] bf16.
 hipError_t tr_probe_launch(const void* src, void* out, int scheme,
                            hipStream_t stream);

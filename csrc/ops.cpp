@@ -579,17 +579,71 @@ torch::Tensor p_from_lse(torch::Tensor scores, c10::optional<torch::Tensor> mask
   return p;
 }
 
-torch::Tensor fa_dot(torch::Tensor dout, torch::Tensor o) {
+// {ddot [B, H, L] f32, dead [ceil(B * H * L / 32)] bool}: one kernel, one read
+// of dout.  dead marks the 32-row tiles of the flat [B * H * L, 64] view whose
+// dout is all +-0.
+std::vector<torch::Tensor> fa_dot_impl(torch::Tensor dout, torch::Tensor o) {
   check_bf16(dout, "dout"); check_bf16(o, "o");
   TORCH_CHECK(dout.dim() == 4 && o.sizes() == dout.sizes(),
               "dout and o must both be [B, H, L, 64]");
   const long n_rows = dout.numel() / dout.size(-1);
   TORCH_CHECK(dout.size(-1) == 64, "fa_dot expects head_dim 64");
   auto d = torch::empty({n_rows}, dout.options().dtype(torch::kFloat32));
-  CHECK_HIP(fa_dot_launch(dout.data_ptr(), o.data_ptr(), d.data_ptr(), n_rows,
-                          cur_stream()));
-  return d.view({dout.size(0), dout.size(1), dout.size(2)});
+  auto dead = torch::empty({(n_rows + 31) / 32},
+                           dout.options().dtype(torch::kBool));
+  CHECK_HIP(fa_dot_launch(dout.data_ptr(), o.data_ptr(), d.data_ptr(),
+                          dead.data_ptr(), n_rows, cur_stream()));
+  return {d.view({dout.size(0), dout.size(1), dout.size(2)}), dead};
 }
+
+torch::Tensor fa_dot(torch::Tensor dout, torch::Tensor o) {
+  return fa_dot_impl(dout, o)[0];
+}
+
+// {ddot, dead [B, H, L / 32] bool}: the flags the backward kernels take.
+std::vector<torch::Tensor> fa_dot_flags(torch::Tensor dout, torch::Tensor o) {
+  TORCH_CHECK(dout.dim() == 4 && dout.size(2) % 32 == 0,
+              "fa_dot_flags needs [B, H, L, 64] with L % 32 == 0");
+  auto r = fa_dot_impl(dout, o);
+  return {r[0], r[1].view({dout.size(0), dout.size(1), dout.size(2) / 32})};
+}
+
+// {ddot, dead} of the packed layout: dout, o [B, L, H * 64].
+std::vector<torch::Tensor> fa_dot_packed_impl(const torch::Tensor& dout,
+                                              const torch::Tensor& o, long B,
+                                              long H, long L) {
+  auto ddot = torch::empty({B, H, L}, dout.options().dtype(torch::kFloat32));
+  auto dead = torch::empty({B, H, L / 32}, dout.options().dtype(torch::kBool));
+  CHECK_HIP(fa_dot_packed_launch(dout.data_ptr(), o.data_ptr(),
+                                 ddot.data_ptr(), dead.data_ptr(), (int)B,
+                                 (int)H, (int)L, cur_stream()));
+  return {ddot, dead};
+}
+
+std::vector<torch::Tensor> fa_dot_packed_flags(torch::Tensor dout,
+                                               torch::Tensor o, long H) {
+  check_bf16(dout, "dout"); check_bf16(o, "o");
+  TORCH_CHECK(dout.dim() == 3 && o.sizes() == dout.sizes() &&
+              dout.size(2) == H * 64 && dout.size(1) % 32 == 0,
+              "dout and o must both be [B, L, H*64] with L % 32 == 0");
+  return fa_dot_packed_impl(dout, o, dout.size(0), H, dout.size(1));
+}
+
+namespace {
+// Optional dead-tile flags for the [B, H, L, 64] backward bindings: bool
+// [B, H, L / 32], as fa_dot_flags returns them.
+const void* flash_dead_ptr(const c10::optional<torch::Tensor>& dead,
+                           const torch::Tensor& x, const FlashDims& d) {
+  if (!dead.has_value()) return nullptr;
+  TORCH_CHECK(dead->scalar_type() == torch::kBool, "dead must be bool");
+  TORCH_CHECK(dead->device() == x.device() && dead->is_contiguous(),
+              "dead must be contiguous and on the attention inputs' device");
+  TORCH_CHECK(dead->dim() == 3 && dead->size(0) == d.B &&
+              dead->size(1) == d.H && dead->size(2) == d.L / 32,
+              "dead must be [B, H, L / 32]");
+  return dead->data_ptr();
+}
+}  // namespace
 
 std::vector<torch::Tensor> flash_bwd_fused(torch::Tensor q, torch::Tensor k,
                                            torch::Tensor v, torch::Tensor dout,
@@ -597,7 +651,8 @@ std::vector<torch::Tensor> flash_bwd_fused(torch::Tensor q, torch::Tensor k,
                                            torch::Tensor lse,
                                            torch::Tensor ddot, double scale,
                                            bool emit_ds,
-                                           c10::optional<torch::Tensor> seg) {
+                                           c10::optional<torch::Tensor> seg,
+                                           c10::optional<torch::Tensor> dead) {
   const auto [B, H, L] = check_flash_bhld(
       "q", q, {{"k", k}, {"v", v}, {"dout", dout}},
       {{"lse", lse}, {"ddot", ddot}});
@@ -605,6 +660,8 @@ std::vector<torch::Tensor> flash_bwd_fused(torch::Tensor q, torch::Tensor k,
   const void* sptr = flash_seg_ptr(seg, mask, q, {B, H, L});
   TORCH_CHECK(!(sptr && emit_ds), "seg with emit_ds=True is not supported: "
               "the flash_dq A/B path is unsegmented");
+  // with emit_ds the kernel ignores the flags: every dS tile is written
+  const void* dptr = flash_dead_ptr(dead, q, {B, H, L});
   // emit_ds=false (the default): no [B, H, L, L] dS materialization — dQ
   // comes from flash_dq_recompute instead.
   auto dk = torch::empty_like(k);
@@ -617,8 +674,8 @@ std::vector<torch::Tensor> flash_bwd_fused(torch::Tensor q, torch::Tensor k,
   }
   CHECK_HIP(flash_bwd_fused_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                                    dout.data_ptr(), mptr, sptr,
-                                   lse.data_ptr(), ddot.data_ptr(), ds_ptr,
-                                   dk.data_ptr(), dv.data_ptr(), (int)B,
+                                   lse.data_ptr(), ddot.data_ptr(), dptr,
+                                   ds_ptr, dk.data_ptr(), dv.data_ptr(), (int)B,
                                    (int)H, (int)L, (float)scale,
                                    cur_stream()));
   if (emit_ds) return {ds, dk, dv};
@@ -690,16 +747,18 @@ namespace {
 std::vector<torch::Tensor> flash_bwd_packed_impl(
     torch::Tensor qkv, torch::Tensor o, torch::Tensor dout,
     c10::optional<torch::Tensor> mask, torch::Tensor lse, long H,
-    double scale, c10::optional<torch::Tensor> seg, bool want_bias) {
+    double scale, c10::optional<torch::Tensor> seg, bool want_bias,
+    bool skip_zero_do) {
   const auto dims = check_flash_packed(qkv, H, {{"o", o}, {"dout", dout}},
                                        {{"lse", lse}});
   const long B = dims.B, L = dims.L;
   const void* mptr = flash_mask_ptr(mask, dims);
   const void* sptr = flash_seg_ptr(seg, mask, qkv, dims);
-  auto ddot = torch::empty({B, H, L}, qkv.options().dtype(torch::kFloat32));
-  CHECK_HIP(fa_dot_packed_launch(dout.data_ptr(), o.data_ptr(),
-                                 ddot.data_ptr(), (int)B, (int)H, (int)L,
-                                 cur_stream()));
+  const auto dd = fa_dot_packed_impl(dout, o, B, H, L);
+  const auto& ddot = dd[0];
+  // the flags are always computed (same kernel, same read of dout);
+  // skip_zero_do only decides whether the two kernels act on them
+  const void* dptr = skip_zero_do ? dd[1].data_ptr() : nullptr;
   auto dqkv = torch::empty_like(qkv);
   torch::Tensor ws;
   void* ws_ptr = nullptr;
@@ -710,11 +769,11 @@ std::vector<torch::Tensor> flash_bwd_packed_impl(
   }
   CHECK_HIP(flash_bwd_fused_packed_launch(
       qkv.data_ptr(), dout.data_ptr(), mptr, sptr, lse.data_ptr(),
-      ddot.data_ptr(), dqkv.data_ptr(), ws_ptr, (int)B, (int)H, (int)L,
+      ddot.data_ptr(), dptr, dqkv.data_ptr(), ws_ptr, (int)B, (int)H, (int)L,
       (float)scale, cur_stream()));
   CHECK_HIP(flash_dq_recompute_packed_launch(
       qkv.data_ptr(), dout.data_ptr(), mptr, sptr, lse.data_ptr(),
-      ddot.data_ptr(), dqkv.data_ptr(), ws_ptr, (int)B, (int)H, (int)L,
+      ddot.data_ptr(), dptr, dqkv.data_ptr(), ws_ptr, (int)B, (int)H, (int)L,
       (float)scale, cur_stream()));
   if (!want_bias) return {dqkv};
   return {dqkv, colsum(ws, ws.size(1), true)};
@@ -726,17 +785,19 @@ torch::Tensor flash_bwd_packed(torch::Tensor qkv, torch::Tensor o,
                                torch::Tensor dout,
                                c10::optional<torch::Tensor> mask,
                                torch::Tensor lse, long H, double scale,
-                               c10::optional<torch::Tensor> seg) {
-  return flash_bwd_packed_impl(qkv, o, dout, mask, lse, H, scale, seg,
-                               false)[0];
+                               c10::optional<torch::Tensor> seg,
+                               bool skip_zero_do) {
+  return flash_bwd_packed_impl(qkv, o, dout, mask, lse, H, scale, seg, false,
+                               skip_zero_do)[0];
 }
 
 // {dqkv, dqkv_bias}: see flash_bwd_packed_impl
 std::vector<torch::Tensor> flash_bwd_packed_bias(
     torch::Tensor qkv, torch::Tensor o, torch::Tensor dout,
     c10::optional<torch::Tensor> mask, torch::Tensor lse, long H,
-    double scale, c10::optional<torch::Tensor> seg) {
-  return flash_bwd_packed_impl(qkv, o, dout, mask, lse, H, scale, seg, true);
+    double scale, c10::optional<torch::Tensor> seg, bool skip_zero_do) {
+  return flash_bwd_packed_impl(qkv, o, dout, mask, lse, H, scale, seg, true,
+                               skip_zero_do);
 }
 
 torch::Tensor flash_dq_recompute(torch::Tensor q, torch::Tensor k,
@@ -744,17 +805,19 @@ torch::Tensor flash_dq_recompute(torch::Tensor q, torch::Tensor k,
                                  c10::optional<torch::Tensor> mask,
                                  torch::Tensor lse, torch::Tensor ddot,
                                  double scale,
-                                 c10::optional<torch::Tensor> seg) {
+                                 c10::optional<torch::Tensor> seg,
+                                 c10::optional<torch::Tensor> dead) {
   const auto [B, H, L] = check_flash_bhld(
       "q", q, {{"k", k}, {"v", v}, {"dout", dout}},
       {{"lse", lse}, {"ddot", ddot}});
   const void* mptr = flash_mask_ptr(mask, {B, H, L});
   const void* sptr = flash_seg_ptr(seg, mask, q, {B, H, L});
+  const void* dptr = flash_dead_ptr(dead, q, {B, H, L});
   auto dq = torch::empty_like(q);
   CHECK_HIP(flash_dq_recompute_launch(q.data_ptr(), k.data_ptr(),
                                       v.data_ptr(), dout.data_ptr(), mptr,
                                       sptr, lse.data_ptr(), ddot.data_ptr(),
-                                      dq.data_ptr(), (int)B, (int)H, (int)L,
+                                      dptr, dq.data_ptr(), (int)B, (int)H, (int)L,
                                       (float)scale, cur_stream()));
   return dq;
 }
@@ -873,12 +936,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused flash bwd: register-accumulated dK/dV (+ optional dS)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"),
         py::arg("mask"), py::arg("lse"), py::arg("ddot"), py::arg("scale"),
-        py::arg("emit_ds") = false, py::arg("seg") = py::none());
+        py::arg("emit_ds") = false, py::arg("seg") = py::none(),
+        py::arg("dead") = py::none());
   m.def("flash_dq_recompute", &flash_dq_recompute,
         "dQ by recompute: S/dP/dS in-register, no dS materialization",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"),
         py::arg("mask"), py::arg("lse"), py::arg("ddot"), py::arg("scale"),
-        py::arg("seg") = py::none());
+        py::arg("seg") = py::none(), py::arg("dead") = py::none());
   m.def("wgrad_gemm", &wgrad_gemm,
         "split-K wgrad GEMM: dW = dy^T @ x (custom MFMA)",
         py::arg("dy"), py::arg("x"), py::arg("splits") = 0);
@@ -890,13 +954,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "full packed flash bwd: ddot + dK/dV + dQ into one [B,L,3D] grad",
         py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("mask"),
         py::arg("lse"), py::arg("H"), py::arg("scale"),
-        py::arg("seg") = py::none());
+        py::arg("seg") = py::none(), py::arg("skip_zero_do") = true);
   m.def("flash_bwd_packed_bias", &flash_bwd_packed_bias,
         "flash_bwd_packed plus the column sum of dqkv (qkv bias grad, bf16)",
         py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("mask"),
         py::arg("lse"), py::arg("H"), py::arg("scale"),
-        py::arg("seg") = py::none());
+        py::arg("seg") = py::none(), py::arg("skip_zero_do") = true);
   m.def("fa_dot", &fa_dot, "rowsum(dO*O) per attention row");
+  m.def("fa_dot_flags", &fa_dot_flags,
+        "fa_dot plus dead [B, H, L/32] bool: query tiles whose dO is all +-0");
+  m.def("fa_dot_packed_flags", &fa_dot_packed_flags,
+        "fa_dot_flags on the packed [B, L, H*64] layout",
+        py::arg("dout"), py::arg("o"), py::arg("H"));
   m.def("flash_dq", &flash_dq, "dQ = dS @ K (MFMA, tr_b16 K^T fragments)");
   m.def("bias_grad", &bias_grad, "bf16 column-sum for linear bias grads");
   m.def("p_from_lse", &p_from_lse, "probabilities from saved logsumexp");

@@ -1,4 +1,12 @@
-"""Standalone flash-attention kernel microbench (for rocprofv3 PMC runs)."""
+"""Standalone flash-attention kernel microbench (for rocprofv3 PMC runs).
+
+    python scripts/bench_flash.py [iters] [--zero-do-tail]
+
+--zero-do-tail zeroes dO where the mask is padding (rows 400..511), as the
+model's backward does, so the dead-query-tile skip has something to skip; the
+three backward kernels (fa_dot, flash_bwd_fused, flash_dq_recompute) are
+reported with and without the flags either way.  With random dO nothing is
+skippable and the pair of figures is the cost of the flag test."""
 import sys, os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import time
 
@@ -9,7 +17,9 @@ from tosem2021_amd import ops
 
 def main():
     B, H, L, dh = 128, 16, 512, 64
-    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 30
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    zero_tail = "--zero-do-tail" in sys.argv[1:]
+    iters = int(args[0]) if args else 30
     torch.manual_seed(0)
     q = torch.randn(B, H, L, dh, device="cuda", dtype=torch.bfloat16)
     k = torch.randn_like(q)
@@ -31,7 +41,35 @@ def main():
     print(f"flash_fwd {dt*1e6:.1f} us/call  {flops/dt/1e12:.1f} TF")
     # bwd stage (round-2 default: dk/dv only, no dS materialization)
     do = torch.randn_like(q)
+    if zero_tail:
+        do[:, :, 400:] = 0
     ddot = ext.fa_dot(do, o)
+
+    # the three backward kernels, without and with the dead-tile flags
+    def timed_us(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / iters * 1e6
+
+    _, dead = ext.fa_dot_flags(do, o)
+    tag = "zero dO tail" if zero_tail else "random dO"
+    print(f"[{tag}: {int(dead.sum())} of {dead.numel()} query tiles dead]")
+    print(f"fa_dot (ddot + flags) {timed_us(lambda: ext.fa_dot(do, o)):.1f} us")
+    # alternating, twice: the first measurement after a change of kernel
+    # reads high, so a pair is compared within one pass
+    for rep in range(2):
+        for name, d in (("no flags", None), ("flags", dead)):
+            t_f = timed_us(lambda: ext.flash_bwd_fused(
+                q, k, v, do, mask, lse, ddot, scale, dead=d))
+            t_q = timed_us(lambda: ext.flash_dq_recompute(
+                q, k, v, do, mask, lse, ddot, scale, dead=d))
+            print(f"pass {rep} {name}: flash_bwd_fused {t_f:.1f} us  "
+                  f"flash_dq_recompute {t_q:.1f} us")
     for _ in range(3):
         dk, dv = ext.flash_bwd_fused(q, k, v, do, mask, lse, ddot, scale)
     torch.cuda.synchronize()
@@ -90,10 +128,15 @@ def main():
 
     qkv = torch.randn(B, L, 3 * H * dh, device="cuda", dtype=torch.bfloat16)
     dop = torch.randn(B, L, H * dh, device="cuda", dtype=torch.bfloat16)
+    if zero_tail:
+        dop[:, 400:] = 0
     o, lse = ext.flash_fwd_packed(qkv, H, mask, scale)
     dt0 = timed(lambda: ext.flash_bwd_packed(qkv, o, dop, mask, lse, H,
                                              scale))
     print(f"flash_bwd_packed {dt0*1e6:.1f} us")
+    dtn = timed(lambda: ext.flash_bwd_packed(qkv, o, dop, mask, lse, H, scale,
+                                             skip_zero_do=False))
+    print(f"flash_bwd_packed skip_zero_do=False {dtn*1e6:.1f} us")
     dqkv = ext.flash_bwd_packed(qkv, o, dop, mask, lse, H, scale)
     dt2 = timed(lambda: dqkv.view(B * L, -1).sum(0))
     print(f"dqkv.sum(0) (the reduce the fold replaces) {dt2*1e6:.1f} us")

@@ -7,11 +7,18 @@ never pass on a non-native path.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
 
 from . import reference
+
+# A/B knob (TOSEM_FLASH_QSKIP=0 disables; default on): the flash backward
+# leaves out 32-row query tiles whose output gradient is all +-0 — the
+# padded rows of a batch.  Bitwise exact for finite inputs, see
+# docs/KERNELS.md "Dead query tiles".  Read per call, so a test can flip it.
+_FLASH_QSKIP = os.environ.get("TOSEM_FLASH_QSKIP", "1") != "0"
 
 _EXT = None
 _EXT_ERR: Optional[str] = None
@@ -401,11 +408,13 @@ class _FlashAttentionFn(torch.autograd.Function):
         if q.is_cuda:
             # two recompute MFMA kernels; dS never touches HBM (round 2 —
             # the round-1 pipeline wrote + re-read a [B, H, L, L] bf16 dS)
-            ddot = hip_ops().fa_dot(do, o)
+            ddot, dead = hip_ops().fa_dot_flags(do, o)
+            if not _FLASH_QSKIP:
+                dead = None
             dk, dv = hip_ops().flash_bwd_fused(q, k, v, do, mask, lse,
-                                               ddot, scale, False, seg)
+                                               ddot, scale, False, seg, dead)
             dq = hip_ops().flash_dq_recompute(q, k, v, do, mask, lse,
-                                              ddot, scale, seg)
+                                              ddot, scale, seg, dead)
             return dq, dk, dv, None, None, None
         bias = reference.segment_bias(seg) if seg is not None else None
         s = torch.matmul(q, k.transpose(-1, -2))
@@ -497,11 +506,13 @@ class _FlashAttentionPackedFn(torch.autograd.Function):
         if qkv.is_cuda:
             if want_bias:
                 dqkv, dbias = hip_ops().flash_bwd_packed_bias(
-                    qkv, o, do, mask, lse, n_heads, scale, seg)
+                    qkv, o, do, mask, lse, n_heads, scale, seg,
+                    _FLASH_QSKIP)
                 # no-op for a bf16 bias
                 return dqkv, None, None, None, None, dbias.to(ctx.qb_dtype)
             dqkv = hip_ops().flash_bwd_packed(qkv, o, do, mask, lse,
-                                              n_heads, scale, seg)
+                                              n_heads, scale, seg,
+                                              _FLASH_QSKIP)
             return dqkv, None, None, None, None, None
         bias = reference.segment_bias(seg) if seg is not None else None
         B, L, D3 = qkv.shape

@@ -261,3 +261,32 @@ def adamw_step_clipped(p, grad, m, v, master, lr, beta1, beta2, eps, wd,
         return
     adamw_step(p, grad, m, v, master, lr, beta1, beta2, eps, wd, step,
                grad_scale=float(clip_state[1]))
+
+
+def dead_q_tiles(dout: torch.Tensor, n_heads: Optional[int] = None
+                 ) -> torch.Tensor:
+    """bool [B, H, L // 32]: True where a 32-row query tile of one head has an
+    output gradient that is all +-0, the flags fa_dot writes next to ddot
+    (csrc/flash_attn.hip).  A tile is live iff any of its 32 x 64 bf16
+    elements has (bits & 0x7fff) != 0: -0.0 counts as zero, the smallest
+    subnormal as live, NaN and inf as live.
+
+    dout: bf16, [B, L, n_heads * 64] (packed) or [B, H, L, 64] (n_heads may
+    then be omitted); L % 32 == 0."""
+    if dout.dtype != torch.bfloat16:
+        raise ValueError("dead_q_tiles expects bf16")
+    if dout.dim() == 3:
+        B, L, D = dout.shape
+        if n_heads is None or D != n_heads * 64:
+            raise ValueError("packed dout must be [B, L, n_heads * 64]")
+        d4 = dout.view(B, L, n_heads, 64).permute(0, 2, 1, 3)
+    elif dout.dim() == 4 and dout.shape[-1] == 64:
+        d4 = dout
+        B, _, L, _ = dout.shape
+    else:
+        raise ValueError("dout must be [B, L, H * 64] or [B, H, L, 64]")
+    if L % 32:
+        raise ValueError("L % 32 == 0 required")
+    bits = d4.contiguous().view(torch.int16).to(torch.int32) & 0x7FFF
+    live = (bits != 0).view(B, d4.shape[1], L // 32, 32 * 64).any(-1)
+    return ~live
