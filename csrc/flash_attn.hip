@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "philox.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(2))) unsigned uint2_t;
@@ -55,6 +56,11 @@ typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
 #define BWD_SEG_LDS_BYTES (BWD_LDS_BYTES + 32 * sizeof(int))
 #define DQ_LDS_BYTES TILE_LDS_BYTES
 #define DQR_LDS_BYTES (2 * TILE_LDS_BYTES + 16)
+// Waves per SIMD flash_dq_recompute is bounded to.  Without dropout it fits
+// two with nothing to spare (254 VGPRs); with the mask's temporaries it
+// spilled 56-112 B per lane under that bound, so the DROP instantiations are
+// bounded to one: lower occupancy, no scratch.
+#define FA_DQR_WAVES(drop) ((drop) ? 1 : 2)
 
 // Tensor geometry: the kernels address q/k/v rows as
 //   base + b*qkv_bs + h*qkv_hs + l*qkv_rs        (64 contiguous shorts)
@@ -408,13 +414,122 @@ struct FaLiveScan {
   }
 };
 
-template <bool SEG>
+// ---- attention-probability dropout -------------------------------------------
+// The mask is philox.h's: one Philox call per 4 x 4 block of P.  A lane's 16
+// score registers are four groups of four consecutive rows (c_row) and its
+// column is lane & 31, so register group g of the four lanes of a quad
+// (lanes 4i .. 4i+3) lies in ONE block, and a 32 x 32 tile costs the quad
+// four calls, one per group.  Each lane runs one of them — lane & 3 = g runs
+// group g's — and the words travel through quad-broadcast DPP moves.  Every
+// lane of the wave must be active at the call: the kernels only branch
+// wave-uniformly around it.
+//
+// Both functions return the keep bits of the lane's 16 registers, bit r =
+// register r, for the two layouts the kernels hold scores in.
+//
+// FA_DROP_QUAD_SHARE=0 builds the A/B variant in which every lane runs all
+// four calls itself and nothing crosses lanes: four times the integer
+// multiplies, no DPP moves.  Same bits; docs/PERF.md has both timings.
+#ifndef FA_DROP_QUAD_SHARE
+#define FA_DROP_QUAD_SHARE 1
+#endif
+
+template <int G>
+__device__ __forceinline__ unsigned fa_quad_bcast(unsigned v) {
+  return (unsigned)__builtin_amdgcn_mov_dpp((int)v, G * 0x55, 0xf, 0xf, true);
+}
+
+// (register = kv, lane = q), forward and dq-recompute.  The lane's q is
+// fixed, so its bits are ONE word (q & 3 = lane & 3) of each group's call, a
+// byte per register.
+template <int G>
+__device__ __forceinline__ unsigned fa_drop_group_kvreg(const unsigned (&w)[4],
+                                                        int i, unsigned thr) {
+  const unsigned t0 = fa_quad_bcast<G>(w[0]), t1 = fa_quad_bcast<G>(w[1]);
+  const unsigned t2 = fa_quad_bcast<G>(w[2]), t3 = fa_quad_bcast<G>(w[3]);
+  const unsigned word = i == 0 ? t0 : i == 1 ? t1 : i == 2 ? t2 : t3;
+  unsigned m = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    m |= (((word >> (8 * j)) & 0xffu) >= thr ? 1u : 0u) << (4 * G + j);
+  return m;
+}
+
+// rowblk: index of block (q / 4, 0) of this lane's (b, h, q);
+// kblk0 = kv0 / 4 + half, the block column of register group 0.
+__device__ __forceinline__ unsigned fa_drop_keep16_kvreg(
+    const FaDrop& dr, unsigned long long rowblk, int kblk0, int lane) {
+  const int i = lane & 3;
+  unsigned w[4];
+#if FA_DROP_QUAD_SHARE
+  fa_drop_block(dr, rowblk + (unsigned)(kblk0 + 2 * i), w);
+  return fa_drop_group_kvreg<0>(w, i, dr.thr) |
+         fa_drop_group_kvreg<1>(w, i, dr.thr) |
+         fa_drop_group_kvreg<2>(w, i, dr.thr) |
+         fa_drop_group_kvreg<3>(w, i, dr.thr);
+#else
+  unsigned m = 0;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    fa_drop_block(dr, rowblk + (unsigned)(kblk0 + 2 * g), w);
+    const unsigned word = i == 0 ? w[0] : i == 1 ? w[1] : i == 2 ? w[2] : w[3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      m |= (((word >> (8 * j)) & 0xffu) >= dr.thr ? 1u : 0u) << (4 * g + j);
+  }
+  return m;
+#endif
+}
+
+// (register = q, lane = kv), flash_bwd_fused.  The lane's kv is fixed: its
+// bits are ONE byte (k & 3 = lane & 3) of every word of each group's call.
+template <int G>
+__device__ __forceinline__ unsigned fa_drop_group_qreg(const unsigned (&w)[4],
+                                                       int sh, unsigned thr) {
+  unsigned m = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    m |= (((fa_quad_bcast<G>(w[j]) >> sh) & 0xffu) >= thr ? 1u : 0u)
+         << (4 * G + j);
+  return m;
+}
+
+// colblk: index of block (0, kv / 4) of this lane's (b, h, kv); nb = L / 4;
+// qblk0 = q0 / 4 + half, the block row of register group 0.
+__device__ __forceinline__ unsigned fa_drop_keep16_qreg(
+    const FaDrop& dr, unsigned long long colblk, unsigned nb, int qblk0,
+    int lane) {
+  const int i = lane & 3;
+  unsigned w[4];
+#if FA_DROP_QUAD_SHARE
+  fa_drop_block(dr, colblk + (unsigned long long)(qblk0 + 2 * i) * nb, w);
+  return fa_drop_group_qreg<0>(w, 8 * i, dr.thr) |
+         fa_drop_group_qreg<1>(w, 8 * i, dr.thr) |
+         fa_drop_group_qreg<2>(w, 8 * i, dr.thr) |
+         fa_drop_group_qreg<3>(w, 8 * i, dr.thr);
+#else
+  unsigned m = 0;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    fa_drop_block(dr, colblk + (unsigned long long)(qblk0 + 2 * g) * nb, w);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      m |= (((w[j] >> (8 * i)) & 0xffu) >= dr.thr ? 1u : 0u) << (4 * g + j);
+  }
+  return m;
+#endif
+}
+
+// DROP: dropout on the probabilities.  The running max, the row sum and lse
+// stay those of the UNDROPPED softmax; the dropped entries of P are zeroed
+// just before the PV product and the scale rides on the epilogue's 1 / l.
+template <bool SEG, bool DROP>
 __global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
                  const short* __restrict__ v, const float* __restrict__ mask,
                  const int* __restrict__ seg,
                  short* __restrict__ o, float* __restrict__ lse,
-                 int B, int H, int L, float scale, FaGeom g) {
+                 int B, int H, int L, float scale, FaGeom g, FaDrop dr) {
   // Each wave processes TWO independent 32-row q-blocks against the shared
   // K/V tile: the second block's MFMAs overlap the first block's serial
   // softmax chain (ILP within the wave).  2 waves/SIMD by registers.
@@ -463,6 +578,13 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
 #pragma unroll
   for (int t = 0; t < 2; ++t) { oA[t] = (f32x16)(0.f); oB[t] = (f32x16)(0.f); }
   float mA = -3.0e38f, lA = 0.f, mB = -3.0e38f, lB = 0.f;
+  // DROP: the mask blocks of this lane's two q rows, block column 0
+  unsigned long long dblkA = 0, dblkB = 0;
+  if constexpr (DROP) {
+    const unsigned long long nb = (unsigned)L / 4;
+    dblkA = ((unsigned long long)qb.bh * nb + (unsigned)(my_qA >> 2)) * nb;
+    dblkB = ((unsigned long long)qb.bh * nb + (unsigned)(my_qB >> 2)) * nb;
+  }
 
   const int n_kv = L / FA_KVB;
   int kt_begin = 0;
@@ -577,6 +699,19 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
       }
     }
 
+    // ---- dropout: the row statistics above saw every probability ----
+    if constexpr (DROP) {
+      const unsigned keepA =
+          fa_drop_keep16_kvreg(dr, dblkA, kv0 / 4 + half, lane);
+      const unsigned keepB =
+          fa_drop_keep16_kvreg(dr, dblkB, kv0 / 4 + half, lane);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (!((keepA >> r) & 1u)) svA[r] = 0.f;
+        if (!((keepB >> r) & 1u)) svB[r] = 0.f;
+      }
+    }
+
     // ---- P -> bf16 A-fragments, both blocks ----
     short8_t pfA[2], pfB[2];
     c_to_afrag2(svA, pfA, svB, pfB);
@@ -604,7 +739,8 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
     if (validA) lse[(long)qb.bh * L + my_qA] = mA + __logf(lA);
     if (validB) lse[(long)qb.bh * L + my_qB] = mB + __logf(lB);
   }
-  const float invA = 1.0f / lA, invB = 1.0f / lB;
+  const float one = DROP ? dr.scale : 1.0f;
+  const float invA = one / lA, invB = one / lB;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     int rloc = c_row(r, half);
@@ -643,25 +779,47 @@ extern "C" int flash_bias_ws_rows(int B, int L) {
 static void fa_fwd_dispatch(const short* q, const short* k, const short* v,
                             const void* mask, const void* seg, void* o,
                             void* lse, int B, int H, int L, float scale,
-                            FaGeom g, hipStream_t stream) {
+                            FaGeom g, FaDrop dr, hipStream_t stream) {
   const dim3 grid = fa_grid(B, H, L, FA_Q2WG);
-  if (seg)
-    flash_fwd_kernel<true><<<grid, FA_BLOCK, FWD_LDS_BYTES, stream>>>(
-        q, k, v, nullptr, (const int*)seg, (short*)o, (float*)lse, B, H, L,
-        scale, g);
+#define FA_FWD_SEG_ARGS                                                       \
+  q, k, v, nullptr, (const int*)seg, (short*)o, (float*)lse, B, H, L, scale,  \
+      g, dr
+#define FA_FWD_ARGS                                                           \
+  q, k, v, (const float*)mask, nullptr, (short*)o, (float*)lse, B, H, L,      \
+      scale, g, dr
+  if (seg && dr.thr)
+    flash_fwd_kernel<true, true><<<grid, FA_BLOCK, FWD_LDS_BYTES, stream>>>(
+        FA_FWD_SEG_ARGS);
+  else if (seg)
+    flash_fwd_kernel<true, false><<<grid, FA_BLOCK, FWD_LDS_BYTES, stream>>>(
+        FA_FWD_SEG_ARGS);
+  else if (dr.thr)
+    flash_fwd_kernel<false, true><<<grid, FA_BLOCK, FWD_LDS_BYTES, stream>>>(
+        FA_FWD_ARGS);
   else
-    flash_fwd_kernel<false><<<grid, FA_BLOCK, FWD_LDS_BYTES, stream>>>(
-        q, k, v, (const float*)mask, nullptr, (short*)o, (float*)lse, B, H, L,
-        scale, g);
+    flash_fwd_kernel<false, false><<<grid, FA_BLOCK, FWD_LDS_BYTES, stream>>>(
+        FA_FWD_ARGS);
+#undef FA_FWD_ARGS
+#undef FA_FWD_SEG_ARGS
 }
+
+// The launchers' dropout words (philox.h): thr = 0 is no dropout, anything
+// above 255 is refused.
+static bool fa_drop_ok(unsigned thr) { return thr <= 255u; }
 
 extern "C" hipError_t flash_fwd_launch(const void* q, const void* k,
                                        const void* v, const void* mask,
                                        const void* seg, void* o, void* lse,
                                        int B, int H, int L, float scale,
+                                       unsigned long long drop_seed,
+                                       unsigned drop_call, unsigned drop_site,
+                                       unsigned drop_thr,
                                        hipStream_t stream) {
+  if (!fa_drop_ok(drop_thr)) return hipErrorInvalidValue;
   fa_fwd_dispatch((const short*)q, (const short*)k, (const short*)v, mask,
-                  seg, o, lse, B, H, L, scale, FaGeom::bhld(H, L), stream);
+                  seg, o, lse, B, H, L, scale, FaGeom::bhld(H, L),
+                  fa_drop_make(drop_seed, drop_call, drop_site, drop_thr),
+                  stream);
   return hipGetLastError();
 }
 
@@ -671,11 +829,18 @@ extern "C" hipError_t flash_fwd_packed_launch(const void* qkv,
                                               const void* seg, void* o,
                                               void* lse, int B, int H, int L,
                                               float scale,
+                                              unsigned long long drop_seed,
+                                              unsigned drop_call,
+                                              unsigned drop_site,
+                                              unsigned drop_thr,
                                               hipStream_t stream) {
+  if (!fa_drop_ok(drop_thr)) return hipErrorInvalidValue;
   const int D = H * FA_DH;
   fa_fwd_dispatch((const short*)qkv, (const short*)qkv + D,
                   (const short*)qkv + 2 * D, mask, seg, o, lse, B, H, L,
-                  scale, FaGeom::packed(H, L), stream);
+                  scale, FaGeom::packed(H, L),
+                  fa_drop_make(drop_seed, drop_call, drop_site, drop_thr),
+                  stream);
   return hipGetLastError();
 }
 
@@ -714,7 +879,15 @@ extern "C" hipError_t flash_fwd_packed_launch(const void* qkv,
 // inside the mirrored fa_seg_range of the workgroup's 128 kv rows are
 // visited.  SEG excludes mask and the dS output.
 
-template <bool SEG, bool BIAS>
+//
+// Dropout (DROP, never with BIAS or the dS output): with keep the forward's
+// mask and Pd = keep * drop_scale * P the forward computed O = Pd V, so
+//   dV = Pd^T dO,   dS = scale * P * (keep * drop_scale * dP - D)
+// with D = rowsum(dO * O) unchanged (O is the dropped output).  keep * P goes
+// into the dV chain and drop_scale onto the accumulator in the epilogue, the
+// mirror of the forward's rounding points.
+
+template <bool SEG, bool BIAS, bool DROP>
 __global__ void __launch_bounds__(FA_BLOCK, 2)
 flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
                        const short* __restrict__ v,
@@ -727,7 +900,7 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
                        short* __restrict__ ds, short* __restrict__ dk,
                        short* __restrict__ dv,
                        int B, int H, int L, float scale, FaGeom g,
-                       float* __restrict__ bias_ws, int bias_ld) {
+                       float* __restrict__ bias_ws, int bias_ld, FaDrop dr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   short* q_lds = (short*)smem;
   short* do_lds = (short*)(smem + TILE_LDS_BYTES);
@@ -759,6 +932,12 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   const int* srow = SEG ? seg + (long)b * L : nullptr;
   int sk = 0;                                         // kv segment id (lane)
   if constexpr (SEG) sk = srow[min(my_kv, L - 1)];
+  // DROP: the mask block of this lane's kv column, block row 0
+  const unsigned drop_nb = (unsigned)L / 4;
+  unsigned long long dblk = 0;
+  if constexpr (DROP)
+    dblk = (unsigned long long)bh * drop_nb * drop_nb +
+           (unsigned)(min(my_kv, L - 1) >> 2);
 
   // Early-out: if every kv row this workgroup owns is padding
   // (bias <= -1e8) and the sequence has at least one real token, P and dS
@@ -872,13 +1051,23 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
 
     // elementwise (lse/ddot by register row, mask bias one scalar per lane)
     float pv[16], gv[16];
+    unsigned keep = 0;
+    if constexpr (DROP)
+      keep = fa_drop_keep16_qreg(dr, dblk, drop_nb, q0 / 4 + half, lane);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int ql = c_row(r, half);
       float bias = mb;
       if constexpr (SEG) bias = sq_r[r] == sk ? 0.f : FA_SEG_BIAS;
-      pv[r] = __expf(s_acc[r] * scale + bias - lse_lds[ql]);
-      gv[r] = scale * pv[r] * (dp_acc[r] - dd_lds[ql]);
+      const float p = __expf(s_acc[r] * scale + bias - lse_lds[ql]);
+      if constexpr (DROP) {
+        const bool kept = (keep >> r) & 1u;
+        pv[r] = kept ? p : 0.f;
+        gv[r] = scale * p * ((kept ? dp_acc[r] * dr.scale : 0.f) - dd_lds[ql]);
+      } else {
+        pv[r] = p;
+        gv[r] = scale * pv[r] * (dp_acc[r] - dd_lds[ql]);
+      }
     }
     // dS out, natural [q, kv] rows (2 B per lane, lanes contiguous in kv);
     // only on the A/B path that feeds flash_dq_kernel
@@ -922,7 +1111,8 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
       int kvl = c_row(r, half);
       if (kv_base + kvl >= L) continue;
       long off = qkv_off + (long)(kv_base + kvl) * g.qkv_rs + 32 * t + col;
-      const short vb = f32_to_bf16(dv_acc[t][r]);
+      const short vb =
+          f32_to_bf16(DROP ? dv_acc[t][r] * dr.scale : dv_acc[t][r]);
       const short kb16 = f32_to_bf16(dk_acc[t][r]);
       dv[off] = vb;
       dk[off] = kb16;
@@ -962,46 +1152,57 @@ static void fa_bwd_fused_dispatch(const short* q, const short* k,
                                   const void* dead, void* ds,
                                   short* dk, short* dv, int B, int H, int L,
                                   float scale, FaGeom g, float* bias_ws,
-                                  hipStream_t stream) {
+                                  FaDrop dr, hipStream_t stream) {
   const dim3 grid = fa_grid(B, H, L, FA_QWG);
   const int bias_ld = 3 * H * FA_DH;
 #define FA_BWD_SEG_ARGS                                                       \
   q, k, v, (const short*)dout, nullptr, (const int*)seg, (const float*)lse,   \
       (const float*)ddot, (const unsigned char*)dead, nullptr, dk, dv, B, H,  \
-      L, scale, g, bias_ws, bias_ld
+      L, scale, g, bias_ws, bias_ld, dr
 #define FA_BWD_ARGS                                                           \
   q, k, v, (const short*)dout, (const float*)mask, nullptr,                   \
       (const float*)lse, (const float*)ddot, (const unsigned char*)dead,      \
-      (short*)ds, dk, dv, B, H, L, scale, g, bias_ws, bias_ld
-  if (seg && bias_ws) {
-    flash_bwd_fused_kernel<true, true><<<grid, FA_BLOCK, BWD_SEG_LDS_BYTES,
-                                         stream>>>(FA_BWD_SEG_ARGS);
+      (short*)ds, dk, dv, B, H, L, scale, g, bias_ws, bias_ld, dr
+  // the callers have refused dropout with bias_ws or ds
+  if (seg && dr.thr) {
+    flash_bwd_fused_kernel<true, false, true>
+        <<<grid, FA_BLOCK, BWD_SEG_LDS_BYTES, stream>>>(FA_BWD_SEG_ARGS);
+  } else if (dr.thr) {
+    flash_bwd_fused_kernel<false, false, true>
+        <<<grid, FA_BLOCK, BWD_LDS_BYTES, stream>>>(FA_BWD_ARGS);
+  } else if (seg && bias_ws) {
+    flash_bwd_fused_kernel<true, true, false>
+        <<<grid, FA_BLOCK, BWD_SEG_LDS_BYTES, stream>>>(FA_BWD_SEG_ARGS);
   } else if (seg) {
-    flash_bwd_fused_kernel<true, false><<<grid, FA_BLOCK, BWD_SEG_LDS_BYTES,
-                                          stream>>>(FA_BWD_SEG_ARGS);
+    flash_bwd_fused_kernel<true, false, false>
+        <<<grid, FA_BLOCK, BWD_SEG_LDS_BYTES, stream>>>(FA_BWD_SEG_ARGS);
   } else if (bias_ws) {
-    flash_bwd_fused_kernel<false, true><<<grid, FA_BLOCK, BWD_LDS_BYTES,
-                                          stream>>>(FA_BWD_ARGS);
+    flash_bwd_fused_kernel<false, true, false>
+        <<<grid, FA_BLOCK, BWD_LDS_BYTES, stream>>>(FA_BWD_ARGS);
   } else {
-    flash_bwd_fused_kernel<false, false><<<grid, FA_BLOCK, BWD_LDS_BYTES,
-                                           stream>>>(FA_BWD_ARGS);
+    flash_bwd_fused_kernel<false, false, false>
+        <<<grid, FA_BLOCK, BWD_LDS_BYTES, stream>>>(FA_BWD_ARGS);
   }
 #undef FA_BWD_ARGS
 #undef FA_BWD_SEG_ARGS
 }
 
-// seg excludes the dS output: with seg given, ds must be nullptr.  dead is
-// ignored when ds is given.
+// seg and dropout exclude the dS output: with either given, ds must be
+// nullptr.  dead is ignored when ds is given.
 extern "C" hipError_t flash_bwd_fused_launch(
     const void* q, const void* k, const void* v, const void* dout,
     const void* mask, const void* seg, const void* lse, const void* ddot,
     const void* dead, void* ds, void* dk, void* dv, int B, int H, int L,
-    float scale, hipStream_t stream) {
-  if (seg && ds) return hipErrorInvalidValue;
+    float scale, unsigned long long drop_seed, unsigned drop_call,
+    unsigned drop_site, unsigned drop_thr, hipStream_t stream) {
+  if ((seg || drop_thr) && ds) return hipErrorInvalidValue;
+  if (!fa_drop_ok(drop_thr)) return hipErrorInvalidValue;
   fa_bwd_fused_dispatch((const short*)q, (const short*)k, (const short*)v,
                         dout, mask, seg, lse, ddot, dead, ds, (short*)dk,
                         (short*)dv, B, H, L, scale, FaGeom::bhld(H, L),
-                        nullptr, stream);
+                        nullptr,
+                        fa_drop_make(drop_seed, drop_call, drop_site, drop_thr),
+                        stream);
   return hipGetLastError();
 }
 
@@ -1011,12 +1212,17 @@ extern "C" hipError_t flash_bwd_fused_launch(
 extern "C" hipError_t flash_bwd_fused_packed_launch(
     const void* qkv, const void* dout, const void* mask, const void* seg,
     const void* lse, const void* ddot, const void* dead, void* dqkv,
-    void* bias_ws, int B, int H, int L, float scale, hipStream_t stream) {
+    void* bias_ws, int B, int H, int L, float scale,
+    unsigned long long drop_seed, unsigned drop_call, unsigned drop_site,
+    unsigned drop_thr, hipStream_t stream) {
+  if (drop_thr && bias_ws) return hipErrorInvalidValue;
+  if (!fa_drop_ok(drop_thr)) return hipErrorInvalidValue;
   const int D = H * FA_DH;
   fa_bwd_fused_dispatch((const short*)qkv, (const short*)qkv + D,
                         (const short*)qkv + 2 * D, dout, mask, seg, lse, ddot,
                         dead, nullptr, (short*)dqkv + D, (short*)dqkv + 2 * D, B, H,
                         L, scale, FaGeom::packed(H, L), (float*)bias_ws,
+                        fa_drop_make(drop_seed, drop_call, drop_site, drop_thr),
                         stream);
   return hipGetLastError();
 }
@@ -1128,8 +1334,10 @@ extern "C" hipError_t flash_dq_launch(const void* ds, const void* k, void* dq,
 //   dQ[q, d] += mfma(dS-frag, K^T-frag), K^T gathered from the staged K tile
 // Segmented (SEG): as in flash_fwd — q ids lane-local, kv ids per register,
 // kv tiles limited to the workgroup's fa_seg_range.
-template <bool SEG, bool BIAS>
-__global__ void __launch_bounds__(FA_BLOCK, 2)
+// Dropout (DROP, never with BIAS): dS = scale * P * (keep * drop_scale * dP
+// - D), the mask drawn as in flash_fwd (same layout, same call).
+template <bool SEG, bool BIAS, bool DROP>
+__global__ void __launch_bounds__(FA_BLOCK, FA_DQR_WAVES(DROP))
 flash_dq_recompute_kernel(const short* __restrict__ q,
                           const short* __restrict__ k,
                           const short* __restrict__ v,
@@ -1141,7 +1349,8 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
                           const unsigned char* __restrict__ dead,
                           short* __restrict__ dq,
                           int B, int H, int L, float scale, FaGeom g,
-                          float* __restrict__ bias_ws, int bias_ld) {
+                          float* __restrict__ bias_ws, int bias_ld,
+                          FaDrop dr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   short* k_lds = (short*)smem;
   short* v_lds = (short*)(smem + TILE_LDS_BYTES);
@@ -1201,6 +1410,13 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   const float lseB = lse[(long)qb.bh * L + (validB ? my_qB : L - 1)];
   const float ddA = ddot[(long)qb.bh * L + (validA ? my_qA : L - 1)];
   const float ddB = ddot[(long)qb.bh * L + (validB ? my_qB : L - 1)];
+  // DROP: the mask blocks of this lane's two q rows, block column 0
+  unsigned long long dblkA = 0, dblkB = 0;
+  if constexpr (DROP) {
+    const unsigned long long nb = (unsigned)L / 4;
+    dblkA = ((unsigned long long)qb.bh * nb + (unsigned)(my_qA >> 2)) * nb;
+    dblkB = ((unsigned long long)qb.bh * nb + (unsigned)(my_qB >> 2)) * nb;
+  }
 
   // bit i of dmask = tile i dead; wave wid owns bits wid (block A) and
   // 4 + wid (block B).  A dead tile's dQ rows are exact zeros.
@@ -1287,6 +1503,11 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
 
     // ---- dS in registers (lse/ddot lane-local, mask by kv register) ----
     float gA[16], gB[16];
+    unsigned keepA = 0, keepB = 0;
+    if constexpr (DROP) {
+      keepA = fa_drop_keep16_kvreg(dr, dblkA, kv0 / 4 + half, lane);
+      keepB = fa_drop_keep16_kvreg(dr, dblkB, kv0 / 4 + half, lane);
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       float mbA, mbB;
@@ -1298,8 +1519,13 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
       }
       float expA = __expf(sA[r] * scale + mbA - lseA);
       float expB = __expf(sB[r] * scale + mbB - lseB);
-      gA[r] = scale * expA * (pA[r] - ddA);
-      gB[r] = scale * expB * (pB[r] - ddB);
+      float dpA = pA[r], dpB = pB[r];
+      if constexpr (DROP) {
+        dpA = (keepA >> r) & 1u ? dpA * dr.scale : 0.f;
+        dpB = (keepB >> r) & 1u ? dpB * dr.scale : 0.f;
+      }
+      gA[r] = scale * expA * (dpA - ddA);
+      gB[r] = scale * expB * (dpB - ddB);
     }
 
     // ---- dS -> A-fragments [row=q][k=kv] ----
@@ -1374,30 +1600,37 @@ static void fa_dq_recompute_dispatch(const short* q, const short* k,
                                      const void* lse, const void* ddot,
                                      const void* dead, void* dq, int B, int H,
                                      int L, float scale, FaGeom g,
-                                     float* bias_ws,
+                                     float* bias_ws, FaDrop dr,
                                      hipStream_t stream) {
   const dim3 grid = fa_grid(B, H, L, FA_Q2WG);
   const int bias_ld = 3 * H * FA_DH;
 #define FA_DQR_SEG_ARGS                                                       \
   q, k, v, (const short*)dout, nullptr, (const int*)seg, (const float*)lse,   \
       (const float*)ddot, (const unsigned char*)dead, (short*)dq, B, H, L,    \
-      scale, g, bias_ws, bias_ld
+      scale, g, bias_ws, bias_ld, dr
 #define FA_DQR_ARGS                                                           \
   q, k, v, (const short*)dout, (const float*)mask, nullptr,                   \
       (const float*)lse, (const float*)ddot, (const unsigned char*)dead,      \
-      (short*)dq, B, H, L, scale, g, bias_ws, bias_ld
-  if (seg && bias_ws) {
-    flash_dq_recompute_kernel<true, true><<<grid, FA_BLOCK, DQR_LDS_BYTES,
-                                            stream>>>(FA_DQR_SEG_ARGS);
+      (short*)dq, B, H, L, scale, g, bias_ws, bias_ld, dr
+  // the callers have refused dropout with bias_ws
+  if (seg && dr.thr) {
+    flash_dq_recompute_kernel<true, false, true>
+        <<<grid, FA_BLOCK, DQR_LDS_BYTES, stream>>>(FA_DQR_SEG_ARGS);
+  } else if (dr.thr) {
+    flash_dq_recompute_kernel<false, false, true>
+        <<<grid, FA_BLOCK, DQR_LDS_BYTES, stream>>>(FA_DQR_ARGS);
+  } else if (seg && bias_ws) {
+    flash_dq_recompute_kernel<true, true, false>
+        <<<grid, FA_BLOCK, DQR_LDS_BYTES, stream>>>(FA_DQR_SEG_ARGS);
   } else if (seg) {
-    flash_dq_recompute_kernel<true, false><<<grid, FA_BLOCK, DQR_LDS_BYTES,
-                                             stream>>>(FA_DQR_SEG_ARGS);
+    flash_dq_recompute_kernel<true, false, false>
+        <<<grid, FA_BLOCK, DQR_LDS_BYTES, stream>>>(FA_DQR_SEG_ARGS);
   } else if (bias_ws) {
-    flash_dq_recompute_kernel<false, true><<<grid, FA_BLOCK, DQR_LDS_BYTES,
-                                             stream>>>(FA_DQR_ARGS);
+    flash_dq_recompute_kernel<false, true, false>
+        <<<grid, FA_BLOCK, DQR_LDS_BYTES, stream>>>(FA_DQR_ARGS);
   } else {
-    flash_dq_recompute_kernel<false, false><<<grid, FA_BLOCK, DQR_LDS_BYTES,
-                                              stream>>>(FA_DQR_ARGS);
+    flash_dq_recompute_kernel<false, false, false>
+        <<<grid, FA_BLOCK, DQR_LDS_BYTES, stream>>>(FA_DQR_ARGS);
   }
 #undef FA_DQR_ARGS
 #undef FA_DQR_SEG_ARGS
@@ -1407,10 +1640,15 @@ extern "C" hipError_t flash_dq_recompute_launch(
     const void* q, const void* k, const void* v, const void* dout,
     const void* mask, const void* seg, const void* lse, const void* ddot,
     const void* dead, void* dq, int B, int H, int L, float scale,
-    hipStream_t stream) {
+    unsigned long long drop_seed, unsigned drop_call, unsigned drop_site,
+    unsigned drop_thr, hipStream_t stream) {
+  if (!fa_drop_ok(drop_thr)) return hipErrorInvalidValue;
   fa_dq_recompute_dispatch((const short*)q, (const short*)k, (const short*)v,
                            dout, mask, seg, lse, ddot, dead, dq, B, H, L, scale,
-                           FaGeom::bhld(H, L), nullptr, stream);
+                           FaGeom::bhld(H, L), nullptr,
+                           fa_drop_make(drop_seed, drop_call, drop_site,
+                                        drop_thr),
+                           stream);
   return hipGetLastError();
 }
 
@@ -1419,13 +1657,19 @@ extern "C" hipError_t flash_dq_recompute_launch(
 extern "C" hipError_t flash_dq_recompute_packed_launch(
     const void* qkv, const void* dout, const void* mask, const void* seg,
     const void* lse, const void* ddot, const void* dead, void* dqkv,
-    void* bias_ws, int B, int H, int L, float scale, hipStream_t stream) {
+    void* bias_ws, int B, int H, int L, float scale,
+    unsigned long long drop_seed, unsigned drop_call, unsigned drop_site,
+    unsigned drop_thr, hipStream_t stream) {
+  if (drop_thr && bias_ws) return hipErrorInvalidValue;
+  if (!fa_drop_ok(drop_thr)) return hipErrorInvalidValue;
   const int D = H * FA_DH;
   fa_dq_recompute_dispatch((const short*)qkv, (const short*)qkv + D,
                            (const short*)qkv + 2 * D, dout, mask, seg, lse,
                            ddot, dead, dqkv, B, H, L, scale,
-                           FaGeom::packed(H, L),
-                           (float*)bias_ws, stream);
+                           FaGeom::packed(H, L), (float*)bias_ws,
+                           fa_drop_make(drop_seed, drop_call, drop_site,
+                                        drop_thr),
+                           stream);
   return hipGetLastError();
 }
 

@@ -122,14 +122,23 @@ hipError_t out_repack_launch(const void* src, void* dst, int B, int L, int H,
 // packed: qkv, dqkv [B, L, 3 * H * 64], o, dout [B, L, H * 64]; lse, ddot
 // [B, H, L] f32.  mask (nullptr = none) [B, L] f32 additive; seg (nullptr =
 // none) [B, L] int32, non-decreasing along a row; at most one of them is set.
+// Dropout on the attention probabilities (philox.h): drop_thr in [1, 255]
+// drops an element iff its random byte is below it, drop_thr = 0 is no
+// dropout; drop_seed, drop_call, drop_site are the mask's key and counter
+// words.  The forward and both backward kernels of one attention call take
+// the same four.  Not together with ds or bias_ws.
 hipError_t flash_fwd_launch(const void* q, const void* k, const void* v,
                             const void* mask, const void* seg, void* o,
                             void* lse, int B, int H, int L, float scale,
+                            unsigned long long drop_seed, unsigned drop_call,
+                            unsigned drop_site, unsigned drop_thr,
                             hipStream_t stream);
 hipError_t flash_fwd_packed_launch(const void* qkv, const void* mask,
                                    const void* seg, void* o, void* lse, int B,
                                    int H, int L, float scale,
-                                   hipStream_t stream);
+                                   unsigned long long drop_seed,
+                                   unsigned drop_call, unsigned drop_site,
+                                   unsigned drop_thr, hipStream_t stream);
 // dead (nullptr = skip nothing) uint8 [B, H, L / 32], as fa_dot writes it:
 // the backward kernels leave out the query tiles it marks, whose dO is all
 // +-0 and whose contribution is exact zeros.
@@ -140,7 +149,10 @@ hipError_t flash_bwd_fused_launch(const void* q, const void* k, const void* v,
                                   const void* seg, const void* lse,
                                   const void* ddot, const void* dead,
                                   void* ds, void* dk, void* dv, int B, int H,
-                                  int L, float scale, hipStream_t stream);
+                                  int L, float scale,
+                                  unsigned long long drop_seed,
+                                  unsigned drop_call, unsigned drop_site,
+                                  unsigned drop_thr, hipStream_t stream);
 // bias_ws (nullptr = none) is [flash_bias_ws_rows(B, L), 3 * H * 64] f32; the
 // fused launcher fills its k and v thirds, the dq launcher its q third.
 hipError_t flash_bwd_fused_packed_launch(const void* qkv, const void* dout,
@@ -148,20 +160,32 @@ hipError_t flash_bwd_fused_packed_launch(const void* qkv, const void* dout,
                                          const void* lse, const void* ddot,
                                          const void* dead, void* dqkv,
                                          void* bias_ws, int B, int H, int L,
-                                         float scale, hipStream_t stream);
+                                         float scale,
+                                         unsigned long long drop_seed,
+                                         unsigned drop_call,
+                                         unsigned drop_site, unsigned drop_thr,
+                                         hipStream_t stream);
 hipError_t flash_dq_recompute_packed_launch(const void* qkv, const void* dout,
                                             const void* mask, const void* seg,
                                             const void* lse, const void* ddot,
                                             const void* dead, void* dqkv,
                                             void* bias_ws, int B, int H, int L,
-                                            float scale, hipStream_t stream);
+                                            float scale,
+                                            unsigned long long drop_seed,
+                                            unsigned drop_call,
+                                            unsigned drop_site,
+                                            unsigned drop_thr,
+                                            hipStream_t stream);
 int flash_bias_ws_rows(int B, int L);
 hipError_t flash_dq_recompute_launch(const void* q, const void* k,
                                      const void* v, const void* dout,
                                      const void* mask, const void* seg,
                                      const void* lse, const void* ddot,
                                      const void* dead, void* dq, int B, int H,
-                                     int L, float scale, hipStream_t stream);
+                                     int L, float scale,
+                                     unsigned long long drop_seed,
+                                     unsigned drop_call, unsigned drop_site,
+                                     unsigned drop_thr, hipStream_t stream);
 // ds [B, H, L, L] bf16.
 hipError_t flash_dq_launch(const void* ds, const void* k, void* dq, int B,
                            int H, int L, hipStream_t stream);

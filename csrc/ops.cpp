@@ -147,6 +147,20 @@ void check_flash_rows(std::initializer_list<NamedTensor> rows,
   }
 }
 
+// Attention-probability dropout words as the flash launchers take them
+// (csrc/philox.h): thr = 0 is no dropout, else thr = round(p * 256) in
+// [1, 255]; seed, call, site select the mask, site = 0x10000 + layer.
+struct FlashDrop { unsigned long long seed; unsigned call, site, thr; };
+
+FlashDrop flash_drop_args(uint64_t seed, int64_t call, int64_t site,
+                          int64_t thr) {
+  TORCH_CHECK(call >= 0 && call <= 0xffffffffLL, "drop_call must fit 32 bits");
+  TORCH_CHECK(site >= 0 && site <= 0xffffffffLL, "drop_site must fit 32 bits");
+  TORCH_CHECK(thr >= 0 && thr <= 255,
+              "attention dropout threshold must be in [0, 255], got ", thr);
+  return {seed, (unsigned)call, (unsigned)site, (unsigned)thr};
+}
+
 // [B, H, L, 64] family: `x` fixes the geometry, every tensor in `same` is
 // bf16 of the same shape, every tensor in `rows` is f32 [B, H, L].
 FlashDims check_flash_bhld(const char* xname, const torch::Tensor& x,
@@ -551,15 +565,19 @@ std::vector<torch::Tensor> flash_fwd(torch::Tensor q, torch::Tensor k,
                                      torch::Tensor v,
                                      c10::optional<torch::Tensor> mask,
                                      double scale,
-                                     c10::optional<torch::Tensor> seg) {
+                                     c10::optional<torch::Tensor> seg,
+                                     uint64_t drop_seed, int64_t drop_call,
+                                     int64_t drop_site, int64_t drop_thr) {
   const auto [B, H, L] = check_flash_bhld("q", q, {{"k", k}, {"v", v}}, {});
+  const auto dr = flash_drop_args(drop_seed, drop_call, drop_site, drop_thr);
   const void* mptr = flash_mask_ptr(mask, {B, H, L});
   const void* sptr = flash_seg_ptr(seg, mask, q, {B, H, L});
   auto o = torch::empty_like(q);
   auto lse = torch::empty({B, H, L}, q.options().dtype(torch::kFloat32));
   CHECK_HIP(flash_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), mptr,
                              sptr, o.data_ptr(), lse.data_ptr(), (int)B,
-                             (int)H, (int)L, (float)scale, cur_stream()));
+                             (int)H, (int)L, (float)scale, dr.seed, dr.call,
+                             dr.site, dr.thr, cur_stream()));
   return {o, lse};
 }
 
@@ -652,7 +670,11 @@ std::vector<torch::Tensor> flash_bwd_fused(torch::Tensor q, torch::Tensor k,
                                            torch::Tensor ddot, double scale,
                                            bool emit_ds,
                                            c10::optional<torch::Tensor> seg,
-                                           c10::optional<torch::Tensor> dead) {
+                                           c10::optional<torch::Tensor> dead,
+                                           uint64_t drop_seed,
+                                           int64_t drop_call,
+                                           int64_t drop_site,
+                                           int64_t drop_thr) {
   const auto [B, H, L] = check_flash_bhld(
       "q", q, {{"k", k}, {"v", v}, {"dout", dout}},
       {{"lse", lse}, {"ddot", ddot}});
@@ -660,6 +682,9 @@ std::vector<torch::Tensor> flash_bwd_fused(torch::Tensor q, torch::Tensor k,
   const void* sptr = flash_seg_ptr(seg, mask, q, {B, H, L});
   TORCH_CHECK(!(sptr && emit_ds), "seg with emit_ds=True is not supported: "
               "the flash_dq A/B path is unsegmented");
+  const auto dr = flash_drop_args(drop_seed, drop_call, drop_site, drop_thr);
+  TORCH_CHECK(!(dr.thr && emit_ds), "dropout with emit_ds=True is not "
+              "supported: the flash_dq A/B path has no dropout");
   // with emit_ds the kernel ignores the flags: every dS tile is written
   const void* dptr = flash_dead_ptr(dead, q, {B, H, L});
   // emit_ds=false (the default): no [B, H, L, L] dS materialization — dQ
@@ -676,8 +701,8 @@ std::vector<torch::Tensor> flash_bwd_fused(torch::Tensor q, torch::Tensor k,
                                    dout.data_ptr(), mptr, sptr,
                                    lse.data_ptr(), ddot.data_ptr(), dptr,
                                    ds_ptr, dk.data_ptr(), dv.data_ptr(), (int)B,
-                                   (int)H, (int)L, (float)scale,
-                                   cur_stream()));
+                                   (int)H, (int)L, (float)scale, dr.seed,
+                                   dr.call, dr.site, dr.thr, cur_stream()));
   if (emit_ds) return {ds, dk, dv};
   return {dk, dv};
 }
@@ -723,9 +748,14 @@ torch::Tensor bias_grad(torch::Tensor dy) {
 std::vector<torch::Tensor> flash_fwd_packed(torch::Tensor qkv, long H,
                                             c10::optional<torch::Tensor> mask,
                                             double scale,
-                                            c10::optional<torch::Tensor> seg) {
+                                            c10::optional<torch::Tensor> seg,
+                                            uint64_t drop_seed,
+                                            int64_t drop_call,
+                                            int64_t drop_site,
+                                            int64_t drop_thr) {
   // qkv: [B, L, 3D] packed projection output, D = H*64
   const auto dims = check_flash_packed(qkv, H, {}, {});
+  const auto dr = flash_drop_args(drop_seed, drop_call, drop_site, drop_thr);
   const long B = dims.B, L = dims.L;
   const void* mptr = flash_mask_ptr(mask, dims);
   const void* sptr = flash_seg_ptr(seg, mask, qkv, dims);
@@ -733,7 +763,8 @@ std::vector<torch::Tensor> flash_fwd_packed(torch::Tensor qkv, long H,
   auto lse = torch::empty({B, H, L}, qkv.options().dtype(torch::kFloat32));
   CHECK_HIP(flash_fwd_packed_launch(qkv.data_ptr(), mptr, sptr, o.data_ptr(),
                                     lse.data_ptr(), (int)B, (int)H, (int)L,
-                                    (float)scale, cur_stream()));
+                                    (float)scale, dr.seed, dr.call, dr.site,
+                                    dr.thr, cur_stream()));
   return {o, lse};
 }
 
@@ -748,9 +779,11 @@ std::vector<torch::Tensor> flash_bwd_packed_impl(
     torch::Tensor qkv, torch::Tensor o, torch::Tensor dout,
     c10::optional<torch::Tensor> mask, torch::Tensor lse, long H,
     double scale, c10::optional<torch::Tensor> seg, bool want_bias,
-    bool skip_zero_do) {
+    bool skip_zero_do, const FlashDrop& dr) {
   const auto dims = check_flash_packed(qkv, H, {{"o", o}, {"dout", dout}},
                                        {{"lse", lse}});
+  TORCH_CHECK(!(dr.thr && want_bias), "attention dropout with the folded qkv "
+              "bias gradient is not supported");
   const long B = dims.B, L = dims.L;
   const void* mptr = flash_mask_ptr(mask, dims);
   const void* sptr = flash_seg_ptr(seg, mask, qkv, dims);
@@ -770,11 +803,11 @@ std::vector<torch::Tensor> flash_bwd_packed_impl(
   CHECK_HIP(flash_bwd_fused_packed_launch(
       qkv.data_ptr(), dout.data_ptr(), mptr, sptr, lse.data_ptr(),
       ddot.data_ptr(), dptr, dqkv.data_ptr(), ws_ptr, (int)B, (int)H, (int)L,
-      (float)scale, cur_stream()));
+      (float)scale, dr.seed, dr.call, dr.site, dr.thr, cur_stream()));
   CHECK_HIP(flash_dq_recompute_packed_launch(
       qkv.data_ptr(), dout.data_ptr(), mptr, sptr, lse.data_ptr(),
       ddot.data_ptr(), dptr, dqkv.data_ptr(), ws_ptr, (int)B, (int)H, (int)L,
-      (float)scale, cur_stream()));
+      (float)scale, dr.seed, dr.call, dr.site, dr.thr, cur_stream()));
   if (!want_bias) return {dqkv};
   return {dqkv, colsum(ws, ws.size(1), true)};
 }
@@ -786,9 +819,12 @@ torch::Tensor flash_bwd_packed(torch::Tensor qkv, torch::Tensor o,
                                c10::optional<torch::Tensor> mask,
                                torch::Tensor lse, long H, double scale,
                                c10::optional<torch::Tensor> seg,
-                               bool skip_zero_do) {
-  return flash_bwd_packed_impl(qkv, o, dout, mask, lse, H, scale, seg, false,
-                               skip_zero_do)[0];
+                               bool skip_zero_do, uint64_t drop_seed,
+                               int64_t drop_call, int64_t drop_site,
+                               int64_t drop_thr) {
+  return flash_bwd_packed_impl(
+      qkv, o, dout, mask, lse, H, scale, seg, false, skip_zero_do,
+      flash_drop_args(drop_seed, drop_call, drop_site, drop_thr))[0];
 }
 
 // {dqkv, dqkv_bias}: see flash_bwd_packed_impl
@@ -797,7 +833,7 @@ std::vector<torch::Tensor> flash_bwd_packed_bias(
     c10::optional<torch::Tensor> mask, torch::Tensor lse, long H,
     double scale, c10::optional<torch::Tensor> seg, bool skip_zero_do) {
   return flash_bwd_packed_impl(qkv, o, dout, mask, lse, H, scale, seg, true,
-                               skip_zero_do);
+                               skip_zero_do, FlashDrop{0, 0, 0, 0});
 }
 
 torch::Tensor flash_dq_recompute(torch::Tensor q, torch::Tensor k,
@@ -806,10 +842,13 @@ torch::Tensor flash_dq_recompute(torch::Tensor q, torch::Tensor k,
                                  torch::Tensor lse, torch::Tensor ddot,
                                  double scale,
                                  c10::optional<torch::Tensor> seg,
-                                 c10::optional<torch::Tensor> dead) {
+                                 c10::optional<torch::Tensor> dead,
+                                 uint64_t drop_seed, int64_t drop_call,
+                                 int64_t drop_site, int64_t drop_thr) {
   const auto [B, H, L] = check_flash_bhld(
       "q", q, {{"k", k}, {"v", v}, {"dout", dout}},
       {{"lse", lse}, {"ddot", ddot}});
+  const auto dr = flash_drop_args(drop_seed, drop_call, drop_site, drop_thr);
   const void* mptr = flash_mask_ptr(mask, {B, H, L});
   const void* sptr = flash_seg_ptr(seg, mask, q, {B, H, L});
   const void* dptr = flash_dead_ptr(dead, q, {B, H, L});
@@ -818,7 +857,8 @@ torch::Tensor flash_dq_recompute(torch::Tensor q, torch::Tensor k,
                                       v.data_ptr(), dout.data_ptr(), mptr,
                                       sptr, lse.data_ptr(), ddot.data_ptr(),
                                       dptr, dq.data_ptr(), (int)B, (int)H, (int)L,
-                                      (float)scale, cur_stream()));
+                                      (float)scale, dr.seed, dr.call, dr.site,
+                                      dr.thr, cur_stream()));
   return dq;
 }
 
@@ -931,30 +971,40 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flash attention fwd (gfx950 MFMA, dh=64); seg: optional int32 "
         "[B, L] non-decreasing segment ids, exclusive with mask",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("mask"),
-        py::arg("scale"), py::arg("seg") = py::none());
+        py::arg("scale"), py::arg("seg") = py::none(),
+        py::arg("drop_seed") = 0, py::arg("drop_call") = 0,
+        py::arg("drop_site") = 0, py::arg("drop_thr") = 0);
   m.def("flash_bwd_fused", &flash_bwd_fused,
         "fused flash bwd: register-accumulated dK/dV (+ optional dS)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"),
         py::arg("mask"), py::arg("lse"), py::arg("ddot"), py::arg("scale"),
         py::arg("emit_ds") = false, py::arg("seg") = py::none(),
-        py::arg("dead") = py::none());
+        py::arg("dead") = py::none(),
+        py::arg("drop_seed") = 0, py::arg("drop_call") = 0,
+        py::arg("drop_site") = 0, py::arg("drop_thr") = 0);
   m.def("flash_dq_recompute", &flash_dq_recompute,
         "dQ by recompute: S/dP/dS in-register, no dS materialization",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"),
         py::arg("mask"), py::arg("lse"), py::arg("ddot"), py::arg("scale"),
-        py::arg("seg") = py::none(), py::arg("dead") = py::none());
+        py::arg("seg") = py::none(), py::arg("dead") = py::none(),
+        py::arg("drop_seed") = 0, py::arg("drop_call") = 0,
+        py::arg("drop_site") = 0, py::arg("drop_thr") = 0);
   m.def("wgrad_gemm", &wgrad_gemm,
         "split-K wgrad GEMM: dW = dy^T @ x (custom MFMA)",
         py::arg("dy"), py::arg("x"), py::arg("splits") = 0);
   m.def("flash_fwd_packed", &flash_fwd_packed,
         "flash fwd on the packed [B,L,3D] QKV projection output",
         py::arg("qkv"), py::arg("H"), py::arg("mask"), py::arg("scale"),
-        py::arg("seg") = py::none());
+        py::arg("seg") = py::none(),
+        py::arg("drop_seed") = 0, py::arg("drop_call") = 0,
+        py::arg("drop_site") = 0, py::arg("drop_thr") = 0);
   m.def("flash_bwd_packed", &flash_bwd_packed,
         "full packed flash bwd: ddot + dK/dV + dQ into one [B,L,3D] grad",
         py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("mask"),
         py::arg("lse"), py::arg("H"), py::arg("scale"),
-        py::arg("seg") = py::none(), py::arg("skip_zero_do") = true);
+        py::arg("seg") = py::none(), py::arg("skip_zero_do") = true,
+        py::arg("drop_seed") = 0, py::arg("drop_call") = 0,
+        py::arg("drop_site") = 0, py::arg("drop_thr") = 0);
   m.def("flash_bwd_packed_bias", &flash_bwd_packed_bias,
         "flash_bwd_packed plus the column sum of dqkv (qkv bias grad, bf16)",
         py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("mask"),

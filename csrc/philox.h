@@ -37,6 +37,47 @@ struct LnDrop {
   float scale;
 };
 
+// ---- attention-probability dropout (flash_attn.hip) --------------------------
+// One call covers one 4 x 4 block of the [L, L] probability matrix of one
+// (b, h), nb = ceil(L / 4) blocks a side:
+//   counter = (blk & 0xffffffff, blk >> 32, site, call),
+//             blk = ((b * H + h) * nb + q / 4) * nb + k / 4 as a 64-bit value
+//   key     = (seed & 0xffffffff, seed >> 32)
+// Output word q & 3 holds row q of the block, its byte k & 3 (byte 0 the
+// lowest) element (q, k); the element is kept iff that byte >= thr.  site is
+// 0x10000 + layer, above every residual site.  A function of (seed, call,
+// layer, b, h, q, k) alone: the three flash kernels hold the scores in two
+// transposed register layouts and draw the same bits.
+//
+// What a launch carries: thr in [1, 255] (0 = no dropout), scale =
+// 256 / (256 - thr), the inverse of the effective keep rate.
+struct FaDrop {
+  unsigned seed_lo, seed_hi, call, site, thr;
+  float scale;
+};
+
+__host__ __device__ __forceinline__ FaDrop fa_drop_make(
+    unsigned long long seed, unsigned call, unsigned site, unsigned thr) {
+  return {(unsigned)seed, (unsigned)(seed >> 32), call, site, thr,
+          256.0f / (float)(256u - thr)};
+}
+
+// The four words of block blk.
+__host__ __device__ __forceinline__ void fa_drop_block(const FaDrop& dr,
+                                                       unsigned long long blk,
+                                                       unsigned (&w)[4]) {
+  w[0] = (unsigned)blk; w[1] = (unsigned)(blk >> 32);
+  w[2] = dr.site; w[3] = dr.call;
+  philox4x32_10(w, dr.seed_lo, dr.seed_hi);
+}
+
+// Element (q, k) of the block whose words are w.
+__host__ __device__ __forceinline__ bool fa_drop_keep(const FaDrop& dr,
+                                                      const unsigned (&w)[4],
+                                                      int q, int k) {
+  return ((w[q & 3] >> (8 * (k & 3))) & 0xffu) >= dr.thr;
+}
+
 // Keep bits of packet pkt: bit j set = element j of the packet is kept.
 __host__ __device__ __forceinline__ unsigned drop_keep8(const LnDrop& dr,
                                                         long pkt) {

@@ -203,6 +203,7 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                      eval_every: int = 0, seed: int = 0,
                      dropout: float = 0.0,
                      fused_dropout: bool = False,
+                     attn_dropout: float = 0.0,
                      pretrain_path: Optional[str] = None,
                      pretrain_steps: int = 0,
                      focal_gamma_property: float = 0.0,
@@ -218,6 +219,11 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
     kernels with a counter-based mask seeded by `seed`
     (MLTCConfig.fused_dropout): no mask tensors, and a resumed run draws the
     masks an uninterrupted one would.
+
+    `attn_dropout` in [0, 1) is the dropout rate on the attention
+    probabilities (MLTCConfig.attn_dropout), applied inside the flash
+    kernels with a counter-based mask seeded by `seed`; on the GPU it needs
+    head_dim 64 and `seq` % 32 == 0.
 
     `max_grad_norm` > 0 clips the global gradient norm and skips steps whose
     gradient is not finite (TrainConfig.max_grad_norm); the result then also
@@ -236,10 +242,12 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
     dev = torch.device(device) if device else (
         torch.device("cuda") if torch.cuda.is_available() else
         torch.device("cpu"))
+    if not 0.0 <= attn_dropout < 1.0:
+        raise ValueError(f"attn_dropout must be in [0, 1), got {attn_dropout}")
     base = CONFIGS[model]
     cfg = MLTCConfig(**{**base.__dict__, "max_seq": seq,
                      "dropout": dropout, "fused_dropout": fused_dropout,
-                     "dropout_seed": seed})
+                     "dropout_seed": seed, "attn_dropout": attn_dropout})
     full = _load_dataset(taxonomy_path, cfg)
     # split_seed pins the train/val partition independently of the training
     # seed, so differently-seeded runs share one val set and their dumped

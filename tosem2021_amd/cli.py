@@ -138,7 +138,7 @@ def cmd_train(args):
         taxonomy_path=args.taxonomy, model=args.model, steps=args.steps,
         batch=args.batch, seq=args.seq, lr=args.lr, ckpt_dir=args.ckpt_dir,
         resume=args.resume, dropout=args.dropout,
-        fused_dropout=args.fused_dropout,
+        fused_dropout=args.fused_dropout, attn_dropout=args.attn_dropout,
         pretrain_path=args.pretrain, pretrain_steps=args.pretrain_steps,
         focal_gamma_property=args.focal_gamma_property,
         label_smoothing=args.label_smoothing, eval_every=args.eval_every,
@@ -146,6 +146,17 @@ def cmd_train(args):
         augment=args.augment, split_seed=args.split_seed, pack=args.pack,
         max_grad_norm=args.clip_grad_norm)
     print(json.dumps(res, indent=2))
+
+
+def _rate(text: str) -> float:
+    """argparse type of a dropout rate: a float in [0, 1)."""
+    try:
+        p = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not 0.0 <= p < 1.0:
+        raise argparse.ArgumentTypeError(f"must be in [0, 1), got {text}")
+    return p
 
 
 def main(argv=None):
@@ -232,6 +243,10 @@ def main(argv=None):
     p.add_argument("--fused-dropout", action="store_true",
                    help="residual dropout inside the add+LayerNorm kernels, "
                         "counter-based mask (reproducible across resume)")
+    p.add_argument("--attn-dropout", type=_rate, default=0.0, metavar="P",
+                   help="dropout on the attention probabilities inside the "
+                        "flash kernels, P in [0, 1); effective rate "
+                        "round(P * 256) / 256")
     p.add_argument("--pretrain", default=None,
                    help="mined taxonomy to pretrain on before fine-tuning")
     p.add_argument("--pretrain-steps", type=int, default=0)

@@ -56,8 +56,22 @@ class MLTCConfig:
     # and torch's global generator.  Another random stream, so a switch.
     fused_dropout: bool = False
     dropout_seed: int = 0
+    # attn_dropout: in training mode, dropout on the attention probabilities
+    # with this rate, inside the flash kernels on the GPU
+    # (ops.flash_attention_packed(dropout=)) and through the same
+    # counter-based mask on the CPU.  Seeded by dropout_seed; independent of
+    # `dropout` and `fused_dropout`.  The effective rate is
+    # round(p * 256) / 256.
+    attn_dropout: float = 0.0
     layer_norm_eps: float = 1e-5
     heads: Dict[str, int] = field(default_factory=lambda: dict(HEAD_SIZES))
+
+    def __post_init__(self):
+        # every way in (YAML model_cfg, train_classifier, the CLI) builds
+        # this dataclass, so the rate is checked here, once
+        if not 0.0 <= self.attn_dropout < 1.0:
+            raise ValueError("attn_dropout must be in [0, 1), got "
+                             f"{self.attn_dropout}")
 
     @property
     def head_dim(self) -> int:
@@ -153,21 +167,27 @@ class Attention(nn.Module):
     softmax between them is the fused gfx950 kernel (csrc/softmax.hip).
     """
 
-    def __init__(self, cfg: MLTCConfig):
+    def __init__(self, cfg: MLTCConfig, layer: int = 0):
         super().__init__()
         self.n_heads = cfg.n_heads
         self.head_dim = cfg.head_dim
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
+        self.layer = layer      # the attention dropout mask's layer word
         self.qkv = nn.Linear(cfg.d_model, 3 * cfg.d_model, bias=True)
         self.proj = nn.Linear(cfg.d_model, cfg.d_model, bias=True)
 
     def forward(self, x, mask_bias: Optional[torch.Tensor],
-                seg: Optional[torch.Tensor] = None, fold_bias: bool = False):
+                seg: Optional[torch.Tensor] = None, fold_bias: bool = False,
+                attn_drop=None):
         """seg: [B, L] int32 segment ids of a packed batch (exclusive with
         mask_bias): attention stays inside each segment.  fold_bias: proj
         runs with its bias detached; the caller routes proj.bias to the
-        LayerNorm that consumes the output (see _FOLD_BIAS_GRAD)."""
+        LayerNorm that consumes the output (see _FOLD_BIAS_GRAD).
+        attn_drop: (p, seed, call) of this forward's dropout on the
+        attention probabilities (never together with fold_bias); the mask
+        is reference.attn_dropout_keep's for this block's layer."""
         B, L, D = x.shape
+        dropout = None if attn_drop is None else (*attn_drop, self.layer)
         if ops.flash_supported(self.head_dim, L):
             # MFMA flash kernels run straight on the packed [B, L, 3D]
             # projection output and write attention out (and, in backward,
@@ -177,9 +197,16 @@ class Attention(nn.Module):
             # gradient, the column sum of the dqkv it writes)
             out = ops.flash_attention_packed(
                 _linear(self.qkv, x, fold_bias), self.n_heads, mask_bias,
-                self.scale, seg, self.qkv.bias if fold_bias else None)
+                self.scale, seg, self.qkv.bias if fold_bias else None,
+                dropout)
             return _linear(self.proj, out, fold_bias)
-        if seg is not None:
+        if dropout is not None and x.is_cuda:
+            # no O(L^2) fallback: P exists only inside the flash kernels
+            raise RuntimeError(
+                "attention dropout on the GPU needs the flash kernels: "
+                f"head_dim 64 and L % 32 == 0, got head_dim {self.head_dim}, "
+                f"L {L}")
+        if seg is not None or dropout is not None:
             if x.is_cuda:
                 # no O(L^2) fallback: packing exists to cut attention work
                 raise RuntimeError(
@@ -187,10 +214,19 @@ class Attention(nn.Module):
                     f"flash kernels: head_dim 64 and L % 32 == 0, got "
                     f"head_dim {self.head_dim}, L {L}")
             # CPU reference for any shape: plain softmax over the
-            # segment bias
+            # segment (or padding) bias, times the reference dropout mask
             q, k, v = ops.qkv_repack(self.qkv(x), self.n_heads)
             s = torch.matmul(q, k.transpose(-1, -2)).float() * self.scale
-            p = torch.softmax(s + ops.reference.segment_bias(seg), dim=-1)
+            if seg is not None:
+                s = s + ops.reference.segment_bias(seg)
+            elif mask_bias is not None:
+                s = s + mask_bias.view(B, 1, 1, L)
+            p = torch.softmax(s, dim=-1)
+            if dropout is not None:
+                keep = ops.reference.attn_dropout_keep(B, self.n_heads, L,
+                                                       *dropout)
+                p = p * keep * ops.reference.attn_dropout_threshold(
+                    dropout[0])[1]
             out = torch.matmul(p.to(v.dtype), v)
             return _linear(self.proj, ops.out_repack(out), fold_bias)
         # general-shape fallback: gather kernel to bmm-ready
@@ -243,10 +279,10 @@ class EncoderBlock(nn.Module):
     consumer of its ffn delta, the next block's ln1 or ln_f, at site 2i + 1.
     """
 
-    def __init__(self, cfg: MLTCConfig):
+    def __init__(self, cfg: MLTCConfig, layer: int = 0):
         super().__init__()
         self.ln1 = FusedLayerNorm(cfg.d_model, cfg.layer_norm_eps)
-        self.attn = Attention(cfg)
+        self.attn = Attention(cfg, layer)
         self.ln2 = FusedLayerNorm(cfg.d_model, cfg.layer_norm_eps)
         self.ffn = FFN(cfg)
         self.dropout = cfg.dropout
@@ -260,10 +296,11 @@ class EncoderBlock(nn.Module):
         return not (self.dropout and self.training)
 
     def forward(self, x, delta, mask_bias, seg=None, delta_bias=None,
-                fold_bias: bool = False, drop=None, index: int = 0):
+                fold_bias: bool = False, drop=None, index: int = 0,
+                attn_drop=None):
         if drop is not None:
             return self._forward_fused_dropout(x, delta, mask_bias, seg, drop,
-                                               index)
+                                               index, attn_drop)
         if delta is None:
             y1 = ops.fused_layernorm(x, self.ln1.weight, self.ln1.bias,
                                      self.ln1.eps)
@@ -273,14 +310,15 @@ class EncoderBlock(nn.Module):
                                              self.ln1.bias, self.ln1.eps,
                                              delta_bias)
         fold_bias = fold_bias and self.fold_ok()
-        h = self._drop(self.attn(y1, mask_bias, seg, fold_bias))
+        h = self._drop(self.attn(y1, mask_bias, seg, fold_bias, attn_drop))
         y2, s2 = ops.fused_add_layernorm(
             s1, h, self.ln2.weight, self.ln2.bias, self.ln2.eps,
             self.attn.proj.bias if fold_bias else None)
         h2 = self._drop(self.ffn(y2, fold_bias))
         return s2, h2
 
-    def _forward_fused_dropout(self, x, delta, mask_bias, seg, drop, index):
+    def _forward_fused_dropout(self, x, delta, mask_bias, seg, drop, index,
+                               attn_drop=None):
         if delta is None:
             y1 = ops.fused_layernorm(x, self.ln1.weight, self.ln1.bias,
                                      self.ln1.eps)
@@ -289,7 +327,7 @@ class EncoderBlock(nn.Module):
             y1, s1 = ops.fused_dropout_add_layernorm(
                 x, delta, self.ln1.weight, self.ln1.bias, self.ln1.eps,
                 *drop, 2 * index - 1)
-        h = self.attn(y1, mask_bias, seg)
+        h = self.attn(y1, mask_bias, seg, attn_drop=attn_drop)
         y2, s2 = ops.fused_dropout_add_layernorm(
             s1, h, self.ln2.weight, self.ln2.bias, self.ln2.eps, *drop,
             2 * index)
@@ -306,15 +344,17 @@ class MLTC(nn.Module):
         super().__init__()
         self.cfg = cfg
         self.fold_bias_grad = fold_bias_grad
-        # fused dropout (cfg.fused_dropout): training-mode forwards so far,
-        # the `call` word of every mask, checkpointed by the Trainer so that
-        # a resumed run draws the masks an uninterrupted one would; and the
-        # data-parallel rank, so that ranks draw different masks
+        # counter-based dropout (cfg.fused_dropout, cfg.attn_dropout):
+        # training-mode forwards so far, the `call` word of every mask,
+        # checkpointed by the Trainer so that a resumed run draws the masks
+        # an uninterrupted one would; and the data-parallel rank, so that
+        # ranks draw different masks
         self.dropout_call = 0
         self.dropout_rank = 0
         self.tok_emb = nn.Embedding(cfg.vocab_size, cfg.d_model)
         self.pos_emb = nn.Embedding(cfg.max_seq, cfg.d_model)
-        self.blocks = nn.ModuleList(EncoderBlock(cfg) for _ in range(cfg.n_layers))
+        self.blocks = nn.ModuleList(EncoderBlock(cfg, i)
+                                    for i in range(cfg.n_layers))
         self.ln_f = FusedLayerNorm(cfg.d_model, cfg.layer_norm_eps)
         self.heads = nn.ModuleDict(
             {name: nn.Linear(cfg.d_model, n) for name, n in cfg.heads.items()}
@@ -338,24 +378,33 @@ class MLTC(nn.Module):
             on = self.fold_bias_grad
         return (on and torch.is_grad_enabled()
                 and not (self.cfg.dropout and self.training)
+                and not (self.cfg.attn_dropout and self.training)
                 and not _USE_FUSED_LINEAR and not _USE_WGRAD)
 
-    def _fused_dropout_args(self):
-        """(p, seed, call) of this forward's fused residual dropout, or None
-        where today's path runs: switch off, dropout 0, or eval mode."""
+    def _dropout_args(self):
+        """((p, seed, call) of this forward's fused residual dropout,
+        (p, seed, call) of its attention dropout), each None where it is
+        inactive: switch off, rate 0, or eval mode.  Both share the seed and
+        the call counter, which advances once per training forward that has
+        either active; their masks differ by site (csrc/philox.h)."""
         cfg = self.cfg
-        if not (cfg.fused_dropout and cfg.dropout and self.training):
-            return None
+        fused = bool(cfg.fused_dropout and cfg.dropout and self.training)
+        attn = bool(cfg.attn_dropout and self.training)
+        if not (fused or attn):
+            return None, None
         call = self.dropout_call
         self.dropout_call += 1
-        return cfg.dropout, cfg.dropout_seed * 65536 + self.dropout_rank, call
+        seed = cfg.dropout_seed * 65536 + self.dropout_rank
+        return ((cfg.dropout, seed, call) if fused else None,
+                (cfg.attn_dropout, seed, call) if attn else None)
 
     def _run_blocks(self, x, mask_bias, seg):
-        drop = self._fused_dropout_args()
+        drop, attn_drop = self._dropout_args()
         if drop is not None:
             delta = None
             for i, blk in enumerate(self.blocks):
-                x, delta = blk(x, delta, mask_bias, seg, drop=drop, index=i)
+                x, delta = blk(x, delta, mask_bias, seg, drop=drop, index=i,
+                               attn_drop=attn_drop)
             if delta is None:
                 return self.ln_f(x)
             x, _ = ops.fused_dropout_add_layernorm(
@@ -365,7 +414,8 @@ class MLTC(nn.Module):
         fold = self._fold_active(x)
         delta = delta_bias = None
         for blk in self.blocks:
-            x, delta = blk(x, delta, mask_bias, seg, delta_bias, fold)
+            x, delta = blk(x, delta, mask_bias, seg, delta_bias, fold,
+                           attn_drop=attn_drop)
             # the bias that belongs to this delta travels on with it
             delta_bias = blk.ffn.down.bias if fold and blk.fold_ok() else None
         if delta is None:

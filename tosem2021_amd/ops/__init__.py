@@ -381,6 +381,42 @@ def lt_linear_gelu_bias(x, w1, b1):
     return hip_ops().lt_linear_gelu_bias(x, w1, b1)
 
 
+def _attn_dropout_words(dropout):
+    """dropout = (p, seed, call, layer) of flash_attention -> None where
+    today's call runs (None or p == 0), else (p, seed, call, layer, site,
+    thr, scale) with the words the Philox key and counter hold."""
+    if dropout is None:
+        return None
+    p, seed, call, layer = dropout
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"attention dropout probability must be in [0, 1), "
+                         f"got {p}")
+    if p == 0:
+        return None
+    thr, scale = reference.attn_dropout_threshold(p)
+    site = (reference.ATTN_DROPOUT_SITE0 + layer) & 0xFFFFFFFF
+    return (p, seed & 0xFFFFFFFFFFFFFFFF, call & 0xFFFFFFFF, layer, site,
+            thr, scale)
+
+
+def _hip_drop(drop):
+    """The bindings' (drop_seed, drop_call, drop_site, drop_thr)."""
+    if drop is None:
+        return ()
+    _, seed, call, _, site, thr, _ = drop
+    return seed, call, site, thr
+
+
+def _cpu_keep_scale(drop, B, H, L, like):
+    """reference.attn_dropout_keep times the scale, in like's dtype: the
+    CPU paths draw the GPU's mask."""
+    if drop is None:
+        return None
+    p, seed, call, layer, _, _, scale = drop
+    keep = reference.attn_dropout_keep(B, H, L, p, seed, call, layer)
+    return keep.to(like.dtype) * scale
+
+
 class _FlashAttentionFn(torch.autograd.Function):
     """Flash attention: MFMA forward (csrc/flash_attn.hip, O(L) memory, saves
     logsumexp); backward = two recompute kernels, O(L) memory end to end:
@@ -388,16 +424,20 @@ class _FlashAttentionFn(torch.autograd.Function):
     (in-register S/dP/dS, accumulates dQ) — no [L, L] dS materialization."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, scale, seg=None):
+    def forward(ctx, q, k, v, mask, scale, seg=None, drop=None):
         if q.is_cuda:
-            o, lse = hip_ops().flash_fwd(q, k, v, mask, scale, seg)
+            o, lse = hip_ops().flash_fwd(q, k, v, mask, scale, seg,
+                                         *_hip_drop(drop))
         else:
             bias = reference.segment_bias(seg) if seg is not None else None
-            o, lse = reference.flash_attention_fwd(q, k, v, mask, scale, bias)
+            ks = _cpu_keep_scale(drop, *q.shape[:3], q)
+            o, lse = reference.flash_attention_fwd(q, k, v, mask, scale, bias,
+                                                   ks)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.mask = mask
         ctx.seg = seg
         ctx.scale = scale
+        ctx.drop = drop
         return o
 
     @staticmethod
@@ -411,20 +451,28 @@ class _FlashAttentionFn(torch.autograd.Function):
             ddot, dead = hip_ops().fa_dot_flags(do, o)
             if not _FLASH_QSKIP:
                 dead = None
+            drop = _hip_drop(ctx.drop)
             dk, dv = hip_ops().flash_bwd_fused(q, k, v, do, mask, lse,
-                                               ddot, scale, False, seg, dead)
+                                               ddot, scale, False, seg, dead,
+                                               *drop)
             dq = hip_ops().flash_dq_recompute(q, k, v, do, mask, lse,
-                                              ddot, scale, seg, dead)
-            return dq, dk, dv, None, None, None
+                                              ddot, scale, seg, dead, *drop)
+            return dq, dk, dv, None, None, None, None
         bias = reference.segment_bias(seg) if seg is not None else None
         s = torch.matmul(q, k.transpose(-1, -2))
         p = reference.p_from_lse(s, mask, lse, scale, bias)
         dp = torch.matmul(do, v.transpose(-1, -2))
+        pd = p
+        ks = _cpu_keep_scale(ctx.drop, *q.shape[:3], q)
+        if ks is not None:
+            # O = (keep * scale * P) V: dP carries the mask, and
+            # softmax_bwd's rowsum(dP * P) is then rowsum(dO * O)
+            dp, pd = dp * ks, p * ks
         dsc = reference.softmax_bwd(dp, p, scale)
         dq = torch.matmul(dsc, k)
         dk = torch.matmul(dsc.transpose(-1, -2), q)
-        dv = torch.matmul(p.transpose(-1, -2), do)
-        return dq, dk, dv, None, None, None
+        dv = torch.matmul(pd.transpose(-1, -2), do)
+        return dq, dk, dv, None, None, None, None
 
 
 def _check_mask_seg(mask, seg):
@@ -446,7 +494,8 @@ def check_segments(seg: torch.Tensor) -> None:
             raise ValueError(f"seg rows {rows} are not non-decreasing")
 
 
-def flash_attention(q, k, v, mask=None, scale: float = 1.0, seg=None):
+def flash_attention(q, k, v, mask=None, scale: float = 1.0, seg=None,
+                    dropout=None):
     """q/k/v: [B, H, L, 64] bf16 contiguous, L % 32 == 0.
 
     mask: optional [B, L] f32 additive key bias; a bias <= -1e8 is treated
@@ -455,10 +504,16 @@ def flash_attention(q, k, v, mask=None, scale: float = 1.0, seg=None):
     exclusive with mask: position i attends to j iff seg[b, i] == seg[b, j].
     Each seg row must be non-decreasing, with the padding tail carrying one
     id above every real id; that is the caller's contract (check_segments
-    verifies it on the host), not checked on the device."""
+    verifies it on the host), not checked on the device.
+
+    dropout: see flash_attention_packed."""
     _check_mask_seg(mask, seg)
+    drop = _attn_dropout_words(dropout)
+    if drop is None:
+        return _FlashAttentionFn.apply(q.contiguous(), k.contiguous(),
+                                       v.contiguous(), mask, scale, seg)
     return _FlashAttentionFn.apply(q.contiguous(), k.contiguous(),
-                                   v.contiguous(), mask, scale, seg)
+                                   v.contiguous(), mask, scale, seg, drop)
 
 
 class _FlashAttentionPackedFn(torch.autograd.Function):
@@ -475,19 +530,22 @@ class _FlashAttentionPackedFn(torch.autograd.Function):
     projection's backward need not re-read dqkv to reduce it."""
 
     @staticmethod
-    def forward(ctx, qkv, n_heads, mask, scale, seg=None, qkv_bias=None):
+    def forward(ctx, qkv, n_heads, mask, scale, seg=None, qkv_bias=None,
+                drop=None):
         ctx.qb_dtype = None if qkv_bias is None else qkv_bias.dtype
+        ctx.drop = drop
         if qkv.is_cuda:
             o, lse = hip_ops().flash_fwd_packed(qkv, n_heads, mask, scale,
-                                                seg)
+                                                seg, *_hip_drop(drop))
         else:
             B, L, D3 = qkv.shape
             d = D3 // 3
             q, k, v = (t.view(B, L, n_heads, 64).transpose(1, 2).contiguous()
                        for t in qkv.split(d, dim=-1))
             bias = reference.segment_bias(seg) if seg is not None else None
+            ks = _cpu_keep_scale(drop, B, n_heads, L, q)
             o4, lse = reference.flash_attention_fwd(q, k, v, mask, scale,
-                                                    bias)
+                                                    bias, ks)
             o = o4.transpose(1, 2).reshape(B, L, d)
         ctx.save_for_backward(qkv, o, lse)
         ctx.n_heads = n_heads
@@ -509,11 +567,13 @@ class _FlashAttentionPackedFn(torch.autograd.Function):
                     qkv, o, do, mask, lse, n_heads, scale, seg,
                     _FLASH_QSKIP)
                 # no-op for a bf16 bias
-                return dqkv, None, None, None, None, dbias.to(ctx.qb_dtype)
+                return (dqkv, None, None, None, None,
+                        dbias.to(ctx.qb_dtype), None)
             dqkv = hip_ops().flash_bwd_packed(qkv, o, do, mask, lse,
                                               n_heads, scale, seg,
-                                              _FLASH_QSKIP)
-            return dqkv, None, None, None, None, None
+                                              _FLASH_QSKIP,
+                                              *_hip_drop(ctx.drop))
+            return dqkv, None, None, None, None, None, None
         bias = reference.segment_bias(seg) if seg is not None else None
         B, L, D3 = qkv.shape
         d = D3 // 3
@@ -523,21 +583,25 @@ class _FlashAttentionPackedFn(torch.autograd.Function):
         s = torch.matmul(q, k.transpose(-1, -2))
         p = reference.p_from_lse(s, mask, lse, scale, bias)
         dp = torch.matmul(do4, v.transpose(-1, -2))
+        pd = p
+        ks = _cpu_keep_scale(ctx.drop, B, n_heads, L, q)
+        if ks is not None:      # as in _FlashAttentionFn.backward
+            dp, pd = dp * ks, p * ks
         dsc = reference.softmax_bwd(dp, p, scale)
         dq = torch.matmul(dsc, k)
         dk = torch.matmul(dsc.transpose(-1, -2), q)
-        dv = torch.matmul(p.transpose(-1, -2), do4)
+        dv = torch.matmul(pd.transpose(-1, -2), do4)
         dqkv = torch.cat(
             [t.transpose(1, 2).reshape(B, L, d) for t in (dq, dk, dv)],
             dim=-1)
         dbias = None
         if want_bias:
             dbias = reference.folded_bias_grad(dqkv).to(ctx.qb_dtype)
-        return dqkv, None, None, None, None, dbias
+        return dqkv, None, None, None, None, dbias, None
 
 
 def flash_attention_packed(qkv, n_heads: int, mask=None, scale: float = 1.0,
-                           seg=None, qkv_bias=None):
+                           seg=None, qkv_bias=None, dropout=None):
     """qkv: [B, L, 3*n_heads*64] bf16 (the fused projection output);
     returns [B, L, n_heads*64] ready for the output projection.
     qkv_bias: see _FlashAttentionPackedFn — the detached-in-forward bias of
@@ -549,10 +613,27 @@ def flash_attention_packed(qkv, n_heads: int, mask=None, scale: float = 1.0,
     exclusive with mask: position i attends to j iff seg[b, i] == seg[b, j].
     Each seg row must be non-decreasing, with the padding tail carrying one
     id above every real id; that is the caller's contract (check_segments
-    verifies it on the host), not checked on the device."""
+    verifies it on the host), not checked on the device.
+
+    dropout: optional (p, seed, call, layer), dropout on the attention
+    probabilities inside the flash kernels: O = (keep * dscale * P) V with
+    keep = reference.attn_dropout_keep(B, H, L, p, seed, call, layer) and
+    (thr, dscale) = reference.attn_dropout_threshold(p) — the effective rate
+    is thr / 256.  The same ints give the same mask in forward and backward,
+    on the GPU and on the CPU; lse stays the undropped softmax's.  None or
+    p == 0 is the call without it; p outside [0, 1) raises ValueError, and
+    so does dropout together with qkv_bias."""
     _check_mask_seg(mask, seg)
+    drop = _attn_dropout_words(dropout)
+    if dropout is not None and qkv_bias is not None:
+        raise ValueError("dropout and qkv_bias are mutually exclusive: the "
+                         "dropout kernels do not emit the folded bias "
+                         "gradient")
+    if drop is None:
+        return _FlashAttentionPackedFn.apply(qkv.contiguous(), n_heads, mask,
+                                             scale, seg, qkv_bias)
     return _FlashAttentionPackedFn.apply(qkv.contiguous(), n_heads, mask,
-                                         scale, seg, qkv_bias)
+                                         scale, seg, None, drop)
 
 
 def flash_supported(head_dim: int, L: int) -> bool:

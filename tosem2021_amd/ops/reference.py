@@ -120,6 +120,45 @@ def dropout_keep(N: int, D: int, p: float, seed: int, call: int,
     return torch.from_numpy((bits >= thr).reshape(N, D))
 
 
+ATTN_DROPOUT_SITE0 = 0x10000   # site of layer 0: above every residual site
+
+
+def attn_dropout_threshold(p: float) -> Tuple[int, float]:
+    """(thr, scale) of attention dropout probability p, 0 < p < 1: a
+    probability is dropped iff its random BYTE is below thr = round(p * 256),
+    clamped to [1, 255]; scale = 256 / (256 - thr) is the inverse of the
+    effective keep rate.  The rate moves in steps of 1/256: p = 0.1 drops
+    26/256 = 0.1016."""
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"dropout probability must be in (0, 1), got {p}")
+    thr = min(max(int(math.floor(p * 256 + 0.5)), 1), 255)
+    return thr, 256 / (256 - thr)
+
+
+def attn_dropout_keep(B: int, H: int, L: int, p: float, seed: int, call: int,
+                      layer: int) -> torch.Tensor:
+    """Keep mask (bool [B, H, L, L], query by key) of the dropout on the
+    attention probabilities: a pure function of (seed, call, layer, b, h, q,
+    k).  One Philox call covers one 4 x 4 block, nb = ceil(L / 4) blocks a
+    side: counter = (blk lo, blk hi, 0x10000 + layer, call) with blk =
+    ((b * H + h) * nb + q // 4) * nb + k // 4, key = (seed lo, seed hi);
+    output word q & 3 holds row q of the block, its byte k & 3 (byte 0 the
+    lowest) element (q, k).  csrc/philox.h holds the same definition for the
+    flash kernels."""
+    thr, _ = attn_dropout_threshold(p)
+    nb = (L + 3) // 4
+    blk = np.arange(B * H * nb * nb, dtype=np.uint64)
+    words = philox4x32_10(
+        (blk & np.uint64(_M32), blk >> np.uint64(32),
+         (ATTN_DROPOUT_SITE0 + layer) & _M32, call & _M32),
+        (seed & _M32, (seed >> 32) & _M32))                     # [P, 4]
+    shifts = np.arange(4, dtype=np.uint32) * np.uint32(8)
+    byte = (words[:, :, None] >> shifts) & np.uint32(0xFF)      # [P, q&3, k&3]
+    keep = (byte >= thr).reshape(B, H, nb, nb, 4, 4)
+    keep = keep.transpose(0, 1, 2, 4, 3, 5).reshape(B, H, 4 * nb, 4 * nb)
+    return torch.from_numpy(np.ascontiguousarray(keep[:, :, :L, :L]))
+
+
 def bias_gelu_fwd(x: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     pre = x.float() + b.float()
     return torch.nn.functional.gelu(pre, approximate="tanh").to(x.dtype)
@@ -162,11 +201,14 @@ def segment_bias(seg: torch.Tensor) -> torch.Tensor:
     return torch.where(same, zero, zero - 1e9).unsqueeze(1)
 
 
-def flash_attention_fwd(q, k, v, mask, scale, bias=None):
+def flash_attention_fwd(q, k, v, mask, scale, bias=None, keep_scale=None):
     """fp32 reference of the flash forward: returns (o in q.dtype, lse f32).
 
     mask: optional [B, L] additive key bias; bias: optional additive bias
-    broadcastable to [B, H, L, L] (segment_bias of a packed batch)."""
+    broadcastable to [B, H, L, L] (segment_bias of a packed batch);
+    keep_scale: optional f32 [B, H, L, L], attn_dropout_keep times the
+    dropout scale — it multiplies the probabilities, lse stays that of the
+    undropped softmax."""
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if mask is not None:
         s = s + mask.float().view(mask.shape[0], 1, 1, -1)
@@ -174,6 +216,8 @@ def flash_attention_fwd(q, k, v, mask, scale, bias=None):
         s = s + bias
     lse = torch.logsumexp(s, dim=-1)
     p = torch.softmax(s, dim=-1)
+    if keep_scale is not None:
+        p = p * keep_scale
     o = torch.matmul(p, v.float())
     return o.to(q.dtype), lse
 
