@@ -105,6 +105,23 @@ hipError_t grad_clip_state_launch(const void* grad, int grad_is_f32, long n,
                                   hipStream_t stream);
 int grad_norm_grid(long n);
 
+// ---- cross_entropy.hip ------------------------------------------------------
+// logits, dlogits [N, V] bf16, V % 8 == 0; target [N] int64; loss_rows, lse,
+// grow [N] f32.  A row whose target is ignore_index or outside [0, V) is
+// ignored: loss 0, gradient row zeros.  loss_rows = lse - logits[target];
+// dlogits = (exp(logits - lse) - [col == target]) * grow[row], every element
+// written.
+hipError_t ce_fwd_launch(const void* logits, const void* target,
+                         void* loss_rows, void* lse, int N, int V,
+                         long ignore_index, hipStream_t stream);
+hipError_t ce_bwd_launch(const void* logits, const void* target,
+                         const void* lse, const void* grow, void* dlogits,
+                         int N, int V, long ignore_index, hipStream_t stream);
+// out [2] f32 = {sum(loss_rows) / n_valid, 1 / n_valid}, {0, 0} with no valid
+// row; one block, fixed order.  N <= 2^24.
+hipError_t ce_mean_launch(const void* loss_rows, const void* target, void* out,
+                          int N, int V, long ignore_index, hipStream_t stream);
+
 // ---- repack.hip -------------------------------------------------------------
 // [B, L, 3, H, dh] <-> [3, B, H, L, dh] (backward = the inverse); dh % 8 == 0.
 hipError_t qkv_repack_launch(const void* src, void* dst, int B, int L, int H,

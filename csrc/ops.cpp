@@ -485,6 +485,70 @@ void adamw_step_clipped(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
                                  cur_stream()));
 }
 
+// Cross-entropy operands (csrc/cross_entropy.hip): logits [N, V] bf16 with
+// V % 8 == 0 and a 16-byte aligned base (16 B per lane loads), target [N]
+// int64 on the same device.  Sets N and V.
+void check_ce(const torch::Tensor& logits, const torch::Tensor& target,
+              long& N, long& V) {
+  check_bf16(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits must be [N, V]");
+  N = logits.size(0);
+  V = logits.size(1);
+  TORCH_CHECK(V > 0, "V must be positive");
+  check_mult8(V, "V");
+  TORCH_CHECK(V <= (1L << 30) && N <= (1L << 24),
+              "cross-entropy supports V <= 2^30 and N <= 2^24");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "logits must be 16-byte aligned");
+  TORCH_CHECK(target.is_contiguous() &&
+              target.scalar_type() == torch::kInt64,
+              "target must be contiguous int64");
+  TORCH_CHECK(target.device() == logits.device(),
+              "target must be on the same device as logits");
+  check_shape(target, "target", {N}, "[N]");
+}
+
+// Returns (mean f32[2] = {mean loss over the valid rows, 1 / n_valid},
+// loss_rows [N] f32, lse [N] f32); nothing is read back here.
+std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits,
+                                             torch::Tensor target,
+                                             long ignore_index) {
+  long N, V;
+  check_ce(logits, target, N, V);
+  auto opts = torch::TensorOptions().dtype(torch::kFloat32)
+                  .device(logits.device());
+  auto loss_rows = torch::empty({N}, opts);
+  auto lse = torch::empty({N}, opts);
+  auto mean = torch::empty({2}, opts);
+  CHECK_HIP(ce_fwd_launch(logits.data_ptr(), target.data_ptr(),
+                          loss_rows.data_ptr(), lse.data_ptr(), (int)N,
+                          (int)V, ignore_index, cur_stream()));
+  CHECK_HIP(ce_mean_launch(loss_rows.data_ptr(), target.data_ptr(),
+                           mean.data_ptr(), (int)N, (int)V, ignore_index,
+                           cur_stream()));
+  return {mean, loss_rows, lse};
+}
+
+torch::Tensor cross_entropy_bwd(torch::Tensor logits, torch::Tensor target,
+                                torch::Tensor lse, torch::Tensor grow,
+                                long ignore_index) {
+  long N, V;
+  check_ce(logits, target, N, V);
+  check_f32(lse, "lse"); check_f32(grow, "grow");
+  TORCH_CHECK(lse.device() == logits.device() &&
+              grow.device() == logits.device(),
+              "lse and grow must be on the same device as logits");
+  check_shape(lse, "lse", {N}, "[N]");
+  check_shape(grow, "grow", {N}, "[N]");
+  // its own buffer; the kernel writes every element
+  auto dlogits = torch::empty_like(logits);
+  CHECK_HIP(ce_bwd_launch(logits.data_ptr(), target.data_ptr(),
+                          lse.data_ptr(), grow.data_ptr(),
+                          dlogits.data_ptr(), (int)N, (int)V, ignore_index,
+                          cur_stream()));
+  return dlogits;
+}
+
 torch::Tensor qkv_repack(torch::Tensor qkv, long H, bool backward) {
   check_bf16(qkv, "qkv");
   TORCH_CHECK(H > 0, "H must be positive");
@@ -1054,6 +1118,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_clip_state", &grad_clip_state,
         "deterministic global grad norm -> device {norm, scale, finite, "
         "sumsq}");
+  m.def("cross_entropy_fwd", &cross_entropy_fwd,
+        "row-wise softmax cross-entropy fwd over bf16 logits [N, V] -> "
+        "({mean, 1 / n_valid}, loss_rows, lse)",
+        py::arg("logits"), py::arg("target"), py::arg("ignore_index") = -100);
+  m.def("cross_entropy_bwd", &cross_entropy_bwd,
+        "cross-entropy bwd: (softmax - onehot) * grow[row], bf16, every "
+        "element written",
+        py::arg("logits"), py::arg("target"), py::arg("lse"),
+        py::arg("grow"), py::arg("ignore_index") = -100);
   m.def("adamw_step_clipped", &adamw_step_clipped,
         "fused AdamW reading its grad scale / skip flag from clip_state");
 }

@@ -31,6 +31,7 @@ ext = CUDAExtension(
         "csrc/softmax.hip",
         "csrc/adamw.hip",
         "csrc/grad_norm.hip",
+        "csrc/cross_entropy.hip",
         "csrc/repack.hip",
         "csrc/flash_attn.hip",
         "csrc/wgrad_gemm.hip",

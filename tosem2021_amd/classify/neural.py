@@ -150,6 +150,49 @@ def _load_dataset(taxonomy_path: str, cfg: MLTCConfig) -> TaxonomyDataset:
     return ds
 
 
+def _epoch_batches(ds: TaxonomyDataset, tok: CodeTokenizer, batch: int,
+                   seq: int, seed: int, epoch: int, device, pack: bool):
+    """One shuffled training epoch of (tokens or PackedBatch, mask, labels):
+    the batch, seq, pack and seed conventions every training stage shares."""
+    if pack:
+        # (PackedBatch, None, labels in segment order)
+        return ((pb, None, lab) for pb, lab in ds.packed_batches(
+            tok, batch, seq, _row_len(seq), device=device,
+            shuffle=True, seed=seed + epoch, drop_last=True))
+    return ds.batches(tok, batch, seq, device=device, shuffle=True,
+                      seed=seed + epoch, drop_last=True)
+
+
+def _run_mlm_steps(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
+                   batch: int, seq: int, steps: int, seed: int, device,
+                   prob: float, pack: bool = False) -> list:
+    """Masked-LM steps on ds's texts (its labels are ignored) until
+    trainer.step_num reaches `steps`.  Each step's corruption is
+    mlm_corrupt(..., seed, trainer.step_num): a function of the batch and
+    the step counter, so a resumed trainer continues the same stream."""
+    from tosem2021_amd.data.mlm import mlm_corrupt
+    losses = []
+    epoch = 0
+    it = iter(())
+    while trainer.step_num < steps:
+        try:
+            toks, mask, _ = next(it)
+        except StopIteration:
+            it = _epoch_batches(ds, tok, batch, seq, seed, epoch, device,
+                                pack)
+            epoch += 1
+            continue
+        clean = toks.tokens if pack else toks
+        corrupted, targets = mlm_corrupt(clean, prob, seed, trainer.step_num,
+                                         tok.vocab_size)
+        if pack:
+            toks.tokens = corrupted
+        else:
+            toks = corrupted
+        losses.append(trainer.step_mlm(toks, mask, targets))
+    return losses
+
+
 def _run_steps(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
                batch: int, seq: int, steps: int, seed: int, device,
                eval_every: int = 0, val_ds: Optional[TaxonomyDataset] = None,
@@ -167,14 +210,8 @@ def _run_steps(trainer: Trainer, ds: TaxonomyDataset, tok: CodeTokenizer,
         try:
             toks, mask, labels = next(it)
         except StopIteration:
-            if pack:
-                # (PackedBatch, None, labels in segment order)
-                it = ((pb, None, lab) for pb, lab in ds.packed_batches(
-                    tok, batch, seq, _row_len(seq), device=device,
-                    shuffle=True, seed=seed + epoch, drop_last=True))
-            else:
-                it = ds.batches(tok, batch, seq, device=device, shuffle=True,
-                                seed=seed + epoch, drop_last=True)
+            it = _epoch_batches(ds, tok, batch, seq, seed, epoch, device,
+                                pack)
             epoch += 1
             continue
         if augment > 0:
@@ -212,7 +249,10 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                      augment: float = 0.0,
                      split_seed: Optional[int] = None,
                      pack: bool = False,
-                     max_grad_norm: float = 0.0) -> dict:
+                     max_grad_norm: float = 0.0,
+                     mlm_path: Optional[str] = None,
+                     mlm_steps: int = 0,
+                     mlm_prob: float = 0.15) -> dict:
     """Fine-tune MLTC on `taxonomy_path`'s labeled rows.
 
     `fused_dropout` runs the residual dropout inside the add+LayerNorm
@@ -238,6 +278,14 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
     pretrained weights with a fresh optimizer + LR schedule — the mined
     corpus stands in for the study's unlabeled test population (reference
     RQs/taxonomy_test2.csv is only its hand-labeled sample).
+
+    With `mlm_path`/`mlm_steps`, the first stage of all is self-supervised
+    masked-LM pretraining of the encoder on that taxonomy's texts, labels
+    ignored (MLTC.mlm_loss, data.mlm.mlm_corrupt with rate `mlm_prob`, the
+    token loss through ops.fused_cross_entropy).  The next stage (the
+    supervised pretrain if there is one, else the fine-tune) warm-starts
+    from its weights in the same way.  The result then also reports
+    `mlm_steps`, `mlm_time_s`, `mlm_loss_first10_mean`, `mlm_final_loss`.
     """
     dev = torch.device(device) if device else (
         torch.device("cuda") if torch.cuda.is_available() else
@@ -270,6 +318,30 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
         trainer.load_or_init()
 
     t0 = time.time()
+    mlm_res = {}
+    mlm_weights = None
+    if mlm_path and mlm_steps > 0 and trainer.step_num == 0:
+        mlm_ds = _load_dataset(mlm_path, cfg)
+        mlm_cfg = TrainConfig(model=model, lr=lr,
+                              warmup_steps=min(50, mlm_steps // 10),
+                              total_steps=mlm_steps, dtype=tcfg.dtype,
+                              max_grad_norm=max_grad_norm)
+        mlm_tr = Trainer(mlm_cfg, device=dev, model_cfg=cfg)
+        mlm_losses = _run_mlm_steps(mlm_tr, mlm_ds, tok, batch, seq,
+                                    mlm_steps, seed, dev, mlm_prob, pack)
+        # warm-start: pretrained weights, fresh optimizer state + schedule
+        mlm_weights = (mlm_tr.flat.flat, mlm_tr.flat.master)
+        trainer.flat.flat.copy_(mlm_weights[0])
+        trainer.flat.master.copy_(mlm_weights[1])
+        del mlm_tr
+        mlm_res = {
+            "mlm_steps": mlm_steps,
+            "mlm_time_s": round(time.time() - t0, 2),
+            "mlm_loss_first10_mean": (sum(mlm_losses[:10]) /
+                                      min(len(mlm_losses), 10)),
+            "mlm_final_loss": mlm_losses[-1],
+        }
+    t0 = time.time()
     pretrain_time = 0.0
     if pretrain_path and pretrain_steps > 0 and trainer.step_num == 0:
         pre_ds = _load_dataset(pretrain_path, cfg)
@@ -280,6 +352,9 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
         pre_tr = Trainer(pre_cfg, device=dev, model_cfg=cfg)
         pre_tr.model.set_pos_weights(
             {k: v.to(dev) for k, v in pre_ds.pos_weights().items()})
+        if mlm_weights is not None:
+            pre_tr.flat.flat.copy_(mlm_weights[0])
+            pre_tr.flat.master.copy_(mlm_weights[1])
         _run_steps(pre_tr, pre_ds, tok, batch, seq, pretrain_steps, seed,
                    dev, eval_every, val_ds, tag="pre ", pack=pack)[0]
         # warm-start: pretrained weights, fresh optimizer state + schedule
@@ -316,6 +391,7 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                 "last_grad_norm": trainer.metrics.get("grad_norm")}
     return {
         **clip,
+        **mlm_res,
         "steps": trainer.step_num,
         "epochs": epoch,
         "train_time_s": round(train_time, 2),

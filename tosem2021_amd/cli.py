@@ -144,7 +144,8 @@ def cmd_train(args):
         label_smoothing=args.label_smoothing, eval_every=args.eval_every,
         seed=args.seed, dump_probs_path=args.dump_probs,
         augment=args.augment, split_seed=args.split_seed, pack=args.pack,
-        max_grad_norm=args.clip_grad_norm)
+        max_grad_norm=args.clip_grad_norm, mlm_path=args.mlm,
+        mlm_steps=args.mlm_steps, mlm_prob=args.mlm_prob)
     print(json.dumps(res, indent=2))
 
 
@@ -250,6 +251,14 @@ def main(argv=None):
     p.add_argument("--pretrain", default=None,
                    help="mined taxonomy to pretrain on before fine-tuning")
     p.add_argument("--pretrain-steps", type=int, default=0)
+    p.add_argument("--mlm", default=None, metavar="PATH",
+                   help="taxonomy whose texts (labels ignored) the encoder "
+                        "is pretrained on as a masked language model, "
+                        "before --pretrain and the fine-tune")
+    p.add_argument("--mlm-steps", type=int, default=0)
+    p.add_argument("--mlm-prob", type=float, default=0.15, metavar="P",
+                   help="fraction of the real tokens selected for "
+                        "prediction in each masked-LM step")
     p.add_argument("--augment", type=float, default=0.0,
                    help="fraction of non-protected token ids consistently "
                         "renamed per example (assertion-text augmentation)")

@@ -435,8 +435,32 @@ class MLTC(nn.Module):
         from packing.pos, attention stays inside packing.seg's segments and
         the pool is per segment: logits are [N, .] in SEGMENT order —
         packing.unpermute() restores the examples' input order."""
+        x = self.encode(tokens, attn_mask, packing)
         if packing is not None:
-            return self._forward_packed(tokens, attn_mask, packing)
+            # per-example mean-pool over the flattened positions
+            R, L, _ = x.shape
+            pooled = ops.segment_mean_pool(x.reshape(R * L, -1),
+                                           packing.seg_start, packing.seg_len,
+                                           packing.pos2seg)
+        else:
+            # masked mean-pool over valid tokens (fused kernel: csrc/pool.hip)
+            pooled = ops.masked_mean_pool(x, attn_mask)
+        return {name: head(pooled) for name, head in self.heads.items()}
+
+    def encode(self, tokens: Optional[torch.Tensor],
+               attn_mask: Optional[torch.Tensor] = None,
+               packing=None) -> torch.Tensor:
+        """The encoder up to and including ln_f: [B, L, D] hidden states
+        ([R, row_len, D] for a packed batch).  Arguments as in forward."""
+        if packing is not None:
+            if attn_mask is not None:
+                raise ValueError("attn_mask and packing are mutually "
+                                 "exclusive: a packed batch carries its own "
+                                 "padding segment")
+            if tokens is None:
+                tokens = packing.tokens
+            x = self.tok_emb(tokens) + self.pos_emb(packing.pos)
+            return self._run_blocks(x, None, packing.seg)
         B, L = tokens.shape
         pos = torch.arange(L, device=tokens.device)
         x = self.tok_emb(tokens) + self.pos_emb(pos)[None, :, :]
@@ -445,24 +469,37 @@ class MLTC(nn.Module):
             mask_bias = torch.where(
                 attn_mask, 0.0, -1e9
             ).to(torch.float32).contiguous()
-        x = self._run_blocks(x, mask_bias, None)
-        # masked mean-pool over valid tokens (fused kernel: csrc/pool.hip)
-        pooled = ops.masked_mean_pool(x, attn_mask)
-        return {name: head(pooled) for name, head in self.heads.items()}
+        return self._run_blocks(x, mask_bias, None)
 
-    def _forward_packed(self, tokens, attn_mask, packing):
-        if attn_mask is not None:
-            raise ValueError("attn_mask and packing are mutually exclusive: "
-                             "a packed batch carries its own padding segment")
-        if tokens is None:
-            tokens = packing.tokens
-        R, L = tokens.shape
-        x = self.tok_emb(tokens) + self.pos_emb(packing.pos)
-        x = self._run_blocks(x, None, packing.seg)
-        # per-example mean-pool over the flattened positions
-        pooled = ops.segment_mean_pool(x.reshape(R * L, -1), packing.seg_start,
-                                       packing.seg_len, packing.pos2seg)
-        return {name: head(pooled) for name, head in self.heads.items()}
+    # rows of the LM-head GEMM come in multiples of this, filled up with
+    # ignored rows: a bounded set of M values for the GEMM library, and the
+    # loss kernel's ignore path runs in every step
+    MLM_ROW_PAD = 256
+
+    def mlm_loss(self, tokens: Optional[torch.Tensor],
+                 attn_mask: Optional[torch.Tensor],
+                 targets: torch.Tensor, packing=None) -> torch.Tensor:
+        """Masked-LM loss (data.mlm.mlm_corrupt makes tokens and targets):
+        mean cross-entropy of predicting targets at the positions where
+        targets != -100, 0-d f32.  The decoder is the token embedding
+        itself (tied weights, no bias, no transform), so the model has no
+        parameter that only this loss uses; tok_emb.weight receives the sum
+        of its embedding and decoder gradients.  Only the selected hidden
+        rows reach the [rows, vocab] logits GEMM and
+        ops.fused_cross_entropy.  Finding them reads the selection's size
+        back from the device, one host sync per call."""
+        h = self.encode(tokens, attn_mask, packing)
+        flat_t = targets.reshape(-1)
+        idx = torch.nonzero(flat_t != -100).flatten()
+        t_sel = flat_t[idx]
+        n_pad = -idx.numel() % self.MLM_ROW_PAD
+        if n_pad:
+            # position 0 is always there; its rows are ignored by the loss
+            idx = torch.cat([idx, idx.new_zeros(n_pad)])
+            t_sel = torch.cat([t_sel, t_sel.new_full((n_pad,), -100)])
+        h_sel = h.reshape(-1, h.shape[-1]).index_select(0, idx)
+        logits = F.linear(h_sel, self.tok_emb.weight)
+        return ops.fused_cross_entropy(logits, t_sel)
 
     def set_pos_weights(self, weights: Dict[str, torch.Tensor]) -> None:
         """Per-class positive weights for the multi-label heads (label

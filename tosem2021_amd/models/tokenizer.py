@@ -13,6 +13,7 @@ from typing import List
 import torch
 
 PAD, CLS, UNK = 0, 1, 2
+MASK = 3    # masked-LM corruption (data/mlm.py); token_id never produces it
 N_RESERVED = 8
 
 _TOKEN_RE = re.compile(

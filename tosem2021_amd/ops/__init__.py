@@ -716,6 +716,76 @@ def segment_mean_pool(x, seg_start, seg_len, pos2seg):
     return _SegmentPoolFn.apply(x.contiguous(), seg_start, seg_len, pos2seg)
 
 
+class _CrossEntropyFn(torch.autograd.Function):
+    """Mean softmax cross-entropy over the non-ignored rows of [N, V]
+    logits (csrc/cross_entropy.hip).  Saves logits, target and the per-row
+    logsumexp; backward recomputes the probabilities from them and writes
+    the gradient into a buffer of its own.  The per-row upstream gradient
+    (upstream scalar / valid rows) is formed on the device: no host sync in
+    either direction."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index):
+        ctx.ignore_index = ignore_index
+        if logits.is_cuda:
+            mean, _, lse = hip_ops().cross_entropy_fwd(logits, target,
+                                                       ignore_index)
+            loss, inv_count = mean[0], mean[1]
+        else:
+            loss_rows, lse = reference.cross_entropy_fwd(logits, target,
+                                                         ignore_index)
+            count = (target != ignore_index).sum()
+            inv_count = torch.where(count > 0, 1.0 / count.clamp(min=1),
+                                    torch.zeros(())).float()
+            loss = loss_rows.sum() * inv_count
+        ctx.save_for_backward(logits, target, lse, inv_count)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, target, lse, inv_count = ctx.saved_tensors
+        grow = (dloss.float() * inv_count).expand(logits.shape[0]).contiguous()
+        if logits.is_cuda:
+            d = hip_ops().cross_entropy_bwd(logits, target, lse, grow,
+                                            ctx.ignore_index)
+        else:
+            d = reference.cross_entropy_bwd(logits, target, lse, grow,
+                                            ctx.ignore_index)
+        return d, None, None
+
+
+def fused_cross_entropy(logits, target, ignore_index: int = -100):
+    """0-d f32 mean of lse(logits[n]) - logits[n, target[n]] over the rows
+    whose target is not ignore_index: F.cross_entropy(logits.float(), target,
+    ignore_index=ignore_index), except that with no valid row the result is
+    0 with zero gradients, not NaN.
+
+    logits [N, V], target [N] int64.  On the GPU the logits must be bf16,
+    contiguous and 16-byte aligned with V % 8 == 0 (ValueError otherwise: no
+    eager fallback), the loss is bitwise reproducible, and a target outside
+    [0, V) is ignored like ignore_index, never used as an index; checking
+    the range would cost a host sync.  On the CPU (any dtype, any V) such a
+    target raises IndexError."""
+    if logits.dim() != 2 or target.shape != logits.shape[:1]:
+        raise ValueError("fused_cross_entropy expects logits [N, V] and "
+                         f"target [N], got {tuple(logits.shape)} and "
+                         f"{tuple(target.shape)}")
+    if target.dtype != torch.int64:
+        raise ValueError("target must be int64")
+    if logits.is_cuda:
+        if logits.dtype != torch.bfloat16:
+            raise ValueError("fused_cross_entropy on the GPU needs bf16 "
+                             f"logits, got {logits.dtype}")
+        if not logits.is_contiguous() or logits.data_ptr() % 16:
+            raise ValueError("fused_cross_entropy on the GPU needs "
+                             "contiguous, 16-byte aligned logits")
+        if logits.shape[1] == 0 or logits.shape[1] % 8:
+            raise ValueError("fused_cross_entropy on the GPU needs V % 8 == "
+                             f"0, got V = {logits.shape[1]}")
+        target = target.contiguous()
+    return _CrossEntropyFn.apply(logits, target, ignore_index)
+
+
 def adamw_step(p, grad, m, v, master, *, lr, beta1=0.9, beta2=0.999, eps=1e-8,
                wd=0.01, step, grad_scale=1.0):
     """Fused AdamW over the flat parameter buffer (see train.py)."""

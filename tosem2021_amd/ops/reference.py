@@ -334,3 +334,46 @@ def dead_q_tiles(dout: torch.Tensor, n_heads: Optional[int] = None
     bits = d4.contiguous().view(torch.int16).to(torch.int32) & 0x7FFF
     live = (bits != 0).view(B, d4.shape[1], L // 32, 32 * 64).any(-1)
     return ~live
+
+
+def _ce_valid(target: torch.Tensor, V: int, ignore_index: int) -> torch.Tensor:
+    """bool [N]: rows that count.  A target that is neither ignore_index nor
+    a column of the logits raises (the HIP kernels treat it as ignored so
+    that it can never index memory; here it is reported)."""
+    valid = target != ignore_index
+    bad = valid & ((target < 0) | (target >= V))
+    if bool(bad.any()):
+        t = int(target[bad][0])
+        raise IndexError(f"cross-entropy target {t} is out of range for "
+                         f"{V} classes (ignore_index {ignore_index})")
+    return valid
+
+
+def cross_entropy_fwd(logits: torch.Tensor, target: torch.Tensor,
+                      ignore_index: int = -100
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Row-wise softmax cross-entropy of csrc/cross_entropy.hip in f32, any
+    dtype and any V: logits [N, V], target [N] int64 -> (loss_rows [N] f32 =
+    lse - logits[target], 0 at ignored rows; lse [N] f32)."""
+    x = logits.float()
+    valid = _ce_valid(target, x.shape[1], ignore_index)
+    lse = torch.logsumexp(x, dim=-1)
+    xt = x.gather(1, target.clamp(min=0).unsqueeze(1)).squeeze(1)
+    loss_rows = torch.where(valid, lse - xt, torch.zeros_like(lse))
+    return loss_rows, lse
+
+
+def cross_entropy_bwd(logits: torch.Tensor, target: torch.Tensor,
+                      lse: torch.Tensor, grow: torch.Tensor,
+                      ignore_index: int = -100) -> torch.Tensor:
+    """dlogits [N, V] in logits.dtype = (exp(logits - lse) - onehot(target))
+    * grow[row]; zeros at ignored rows.  grow [N] f32 is the per-row
+    upstream gradient."""
+    x = logits.float()
+    valid = _ce_valid(target, x.shape[1], ignore_index)
+    p = torch.exp(x - lse.unsqueeze(1))
+    p.scatter_add_(1, target.clamp(min=0).unsqueeze(1),
+                   -torch.ones_like(lse).unsqueeze(1))
+    d = p * grow.unsqueeze(1)
+    return torch.where(valid.unsqueeze(1), d, torch.zeros_like(d)).to(
+        logits.dtype)

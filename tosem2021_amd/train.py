@@ -192,10 +192,29 @@ class Trainer:
              labels: Dict[str, torch.Tensor]) -> float:
         """tokens: [B, L] tensor, or a PackedBatch with attn_mask None and
         the labels in segment order (TaxonomyDataset.packed_batches)."""
+        return self._step(
+            lambda: self.model.loss(self._forward(tokens, attn_mask), labels))
+
+    def step_mlm(self, tokens, attn_mask: Optional[torch.Tensor],
+                 targets: torch.Tensor) -> float:
+        """One masked-LM pretraining step (MLTC.mlm_loss): tokens is the
+        corrupted [B, L] batch, or a PackedBatch whose .tokens are corrupted
+        (attn_mask None); targets has the tokens' shape, -100 where nothing
+        is predicted (data.mlm.mlm_corrupt).  The classification heads get
+        no gradient in such a step; ddp.finalize reduces their buckets all
+        the same, so the ranks stay in step."""
+        if isinstance(tokens, PackedBatch):
+            return self._step(lambda: self.model.mlm_loss(
+                tokens.tokens, attn_mask, targets, packing=tokens))
+        return self._step(
+            lambda: self.model.mlm_loss(tokens, attn_mask, targets))
+
+    def _step(self, loss_fn) -> float:
+        """zero_grad, loss_fn() -> scalar loss, backward, all-reduce, AdamW,
+        bookkeeping: the body step and step_mlm share."""
         with trace("train_step", step=self.step_num + 1):
             self.flat.zero_grad()
-            logits = self._forward(tokens, attn_mask)
-            loss = self.model.loss(logits, labels)
+            loss = loss_fn()
             loss.backward()
             self.ddp.finalize()
             self.step_num += 1
