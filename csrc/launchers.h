@@ -98,6 +98,24 @@ hipError_t adamw_clipped_launch(void* p_bf16, const void* grad,
                                 void* master, long n, float lr, float beta1,
                                 float beta2, float eps, float wd, int step,
                                 const void* clip_state, hipStream_t stream);
+// Parameter groups: seg_end [n_seg] int64, strictly increasing exclusive end
+// offsets with seg_end[n_seg - 1] == n; seg_lr_mult, seg_wd [n_seg] f32; all
+// on the device, 1 <= n_seg <= 1024 (hipErrorInvalidValue otherwise).
+// Element e of the first segment s with e < seg_end[s] is updated as
+// adamw_launch would with lr * seg_lr_mult[s] and wd = seg_wd[s].
+hipError_t adamw_grouped_launch(void* p_bf16, const void* grad,
+                                int grad_is_f32, void* m, void* v,
+                                void* master, long n, float lr, float beta1,
+                                float beta2, float eps, int step,
+                                const void* seg_end, const void* seg_lr_mult,
+                                const void* seg_wd, int n_seg,
+                                float grad_scale, hipStream_t stream);
+hipError_t adamw_grouped_clipped_launch(
+    void* p_bf16, const void* grad, int grad_is_f32, void* m, void* v,
+    void* master, long n, float lr, float beta1, float beta2, float eps,
+    int step, const void* seg_end, const void* seg_lr_mult,
+    const void* seg_wd, int n_seg, const void* clip_state,
+    hipStream_t stream);
 // partials is [grad_norm_grid(n)] f32; n % 8 == 0.
 hipError_t grad_clip_state_launch(const void* grad, int grad_is_f32, long n,
                                   float grad_scale, float max_norm,

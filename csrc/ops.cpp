@@ -485,6 +485,72 @@ void adamw_step_clipped(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
                                  cur_stream()));
 }
 
+// The segment table of the grouped AdamW step: seg_end int64, seg_lr_mult
+// and seg_wd f32, one length 1 <= S <= 1024, contiguous, on the device.
+// That seg_end increases strictly up to n is checked on the host table
+// before upload (tosem2021_amd.ops.check_segment_table), not read back here.
+int check_segment_table(const torch::Tensor& seg_end,
+                        const torch::Tensor& seg_lr_mult,
+                        const torch::Tensor& seg_wd) {
+  TORCH_CHECK(seg_end.is_contiguous() && seg_end.device().is_cuda() &&
+              seg_end.scalar_type() == torch::kInt64 && seg_end.dim() == 1,
+              "seg_end must be a contiguous 1-D int64 tensor on the GPU");
+  check_f32(seg_lr_mult, "seg_lr_mult"); check_f32(seg_wd, "seg_wd");
+  const long S = seg_end.numel();
+  TORCH_CHECK(seg_lr_mult.dim() == 1 && seg_wd.dim() == 1 &&
+              seg_lr_mult.numel() == S && seg_wd.numel() == S,
+              "seg_end, seg_lr_mult and seg_wd must have one length");
+  TORCH_CHECK(S >= 1 && S <= 1024,
+              "the segment table holds 1 to 1024 segments, got ", S);
+  return (int)S;
+}
+
+void adamw_step_grouped(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
+                        torch::Tensor v, torch::Tensor master,
+                        torch::Tensor seg_end, torch::Tensor seg_lr_mult,
+                        torch::Tensor seg_wd, double lr, double beta1,
+                        double beta2, double eps, long step,
+                        double grad_scale) {
+  check_bf16(p, "p"); check_f32(m, "m"); check_f32(v, "v");
+  check_f32(master, "master");
+  TORCH_CHECK(grad.is_contiguous() && grad.device().is_cuda(), "bad grad");
+  int gf32 = grad.scalar_type() == torch::kFloat32;
+  TORCH_CHECK(gf32 || grad.scalar_type() == torch::kBFloat16,
+              "grad must be f32 or bf16");
+  const long n = p.numel();
+  TORCH_CHECK(n % 4 == 0, "flat parameter buffer must be padded to 4 elems");
+  TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n &&
+              master.numel() == n, "size mismatch");
+  int S = check_segment_table(seg_end, seg_lr_mult, seg_wd);
+  CHECK_HIP(adamw_grouped_launch(
+      p.data_ptr(), grad.data_ptr(), gf32, m.data_ptr(), v.data_ptr(),
+      master.data_ptr(), n, (float)lr, (float)beta1, (float)beta2, (float)eps,
+      (int)step, seg_end.data_ptr(), seg_lr_mult.data_ptr(),
+      seg_wd.data_ptr(), S, (float)grad_scale, cur_stream()));
+}
+
+void adamw_step_grouped_clipped(torch::Tensor p, torch::Tensor grad,
+                                torch::Tensor m, torch::Tensor v,
+                                torch::Tensor master, torch::Tensor seg_end,
+                                torch::Tensor seg_lr_mult,
+                                torch::Tensor seg_wd, double lr, double beta1,
+                                double beta2, double eps, long step,
+                                torch::Tensor clip_state) {
+  check_bf16(p, "p"); check_f32(m, "m"); check_f32(v, "v");
+  check_f32(master, "master"); check_f32(clip_state, "clip_state");
+  int gf32 = check_flat_grad(grad);
+  TORCH_CHECK(clip_state.numel() == 4, "clip_state must hold 4 floats");
+  const long n = p.numel();
+  TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n &&
+              master.numel() == n, "size mismatch");
+  int S = check_segment_table(seg_end, seg_lr_mult, seg_wd);
+  CHECK_HIP(adamw_grouped_clipped_launch(
+      p.data_ptr(), grad.data_ptr(), gf32, m.data_ptr(), v.data_ptr(),
+      master.data_ptr(), n, (float)lr, (float)beta1, (float)beta2, (float)eps,
+      (int)step, seg_end.data_ptr(), seg_lr_mult.data_ptr(),
+      seg_wd.data_ptr(), S, clip_state.data_ptr(), cur_stream()));
+}
+
 // Cross-entropy operands (csrc/cross_entropy.hip): logits [N, V] bf16 with
 // V % 8 == 0 and a 16-byte aligned base (16 B per lane loads), target [N]
 // int64 on the same device.  Sets N and V.
@@ -1129,4 +1195,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("grow"), py::arg("ignore_index") = -100);
   m.def("adamw_step_clipped", &adamw_step_clipped,
         "fused AdamW reading its grad scale / skip flag from clip_state");
+  m.def("adamw_step_grouped", &adamw_step_grouped,
+        "fused AdamW with per-segment lr multiplier and weight decay");
+  m.def("adamw_step_grouped_clipped", &adamw_step_grouped_clipped,
+        "adamw_step_grouped reading its grad scale / skip flag from "
+        "clip_state");
 }

@@ -252,7 +252,10 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                      max_grad_norm: float = 0.0,
                      mlm_path: Optional[str] = None,
                      mlm_steps: int = 0,
-                     mlm_prob: float = 0.15) -> dict:
+                     mlm_prob: float = 0.15,
+                     weight_decay: float = 0.01,
+                     no_decay_1d: bool = False,
+                     layer_decay: float = 1.0) -> dict:
     """Fine-tune MLTC on `taxonomy_path`'s labeled rows.
 
     `fused_dropout` runs the residual dropout inside the add+LayerNorm
@@ -268,6 +271,15 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
     `max_grad_norm` > 0 clips the global gradient norm and skips steps whose
     gradient is not finite (TrainConfig.max_grad_norm); the result then also
     reports `skipped_steps` and `last_grad_norm`.
+
+    `weight_decay` is AdamW's decoupled weight decay and `no_decay_1d` keeps
+    it off every 1-D parameter (LayerNorm gains and biases, projection
+    biases); both apply to every stage.  `layer_decay` in (0, 1] is
+    layer-wise LR decay (TrainConfig.layer_decay): the heads train at the
+    scheduled rate and each layer below at `layer_decay` times the rate of
+    the one above.  It applies to the final fine-tune stage only; the MLM
+    and supervised pretraining stages train from scratch, where a smaller
+    rate at the bottom only slows them.
 
     `pack` trains and evaluates on packed batches (data.packing): each
     step's `batch` examples share rows of `seq` tokens instead of one padded
@@ -306,7 +318,8 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
     tcfg = TrainConfig(model=model, lr=lr, warmup_steps=min(50, steps // 10),
                        total_steps=steps, ckpt_dir=ckpt_dir,
                        dtype="bf16" if dev.type == "cuda" else "f32",
-                       max_grad_norm=max_grad_norm)
+                       max_grad_norm=max_grad_norm, weight_decay=weight_decay,
+                       no_decay_1d=no_decay_1d, layer_decay=layer_decay)
     trainer = Trainer(tcfg, device=dev, model_cfg=cfg)
     trainer.model.set_pos_weights(
         {k: v.to(dev) for k, v in train_ds.pos_weights().items()})
@@ -325,7 +338,9 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
         mlm_cfg = TrainConfig(model=model, lr=lr,
                               warmup_steps=min(50, mlm_steps // 10),
                               total_steps=mlm_steps, dtype=tcfg.dtype,
-                              max_grad_norm=max_grad_norm)
+                              max_grad_norm=max_grad_norm,
+                              weight_decay=weight_decay,
+                              no_decay_1d=no_decay_1d)
         mlm_tr = Trainer(mlm_cfg, device=dev, model_cfg=cfg)
         mlm_losses = _run_mlm_steps(mlm_tr, mlm_ds, tok, batch, seq,
                                     mlm_steps, seed, dev, mlm_prob, pack)
@@ -348,7 +363,9 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
         pre_cfg = TrainConfig(model=model, lr=lr,
                               warmup_steps=min(50, pretrain_steps // 10),
                               total_steps=pretrain_steps,
-                              dtype=tcfg.dtype, max_grad_norm=max_grad_norm)
+                              dtype=tcfg.dtype, max_grad_norm=max_grad_norm,
+                              weight_decay=weight_decay,
+                              no_decay_1d=no_decay_1d)
         pre_tr = Trainer(pre_cfg, device=dev, model_cfg=cfg)
         pre_tr.model.set_pos_weights(
             {k: v.to(dev) for k, v in pre_ds.pos_weights().items()})

@@ -145,7 +145,9 @@ def cmd_train(args):
         seed=args.seed, dump_probs_path=args.dump_probs,
         augment=args.augment, split_seed=args.split_seed, pack=args.pack,
         max_grad_norm=args.clip_grad_norm, mlm_path=args.mlm,
-        mlm_steps=args.mlm_steps, mlm_prob=args.mlm_prob)
+        mlm_steps=args.mlm_steps, mlm_prob=args.mlm_prob,
+        weight_decay=args.weight_decay, no_decay_1d=args.no_decay_1d,
+        layer_decay=args.layer_decay)
     print(json.dumps(res, indent=2))
 
 
@@ -278,6 +280,16 @@ def main(argv=None):
     p.add_argument("--clip-grad-norm", type=float, default=0.0,
                    help="clip the global gradient norm to this value and "
                         "skip steps with a non-finite gradient (0 = off)")
+    p.add_argument("--weight-decay", type=float, default=0.01, metavar="X",
+                   help="AdamW's decoupled weight decay, every stage")
+    p.add_argument("--no-decay-1d", action="store_true",
+                   help="no weight decay on 1-D parameters (LayerNorm gains "
+                        "and biases, projection biases), every stage")
+    p.add_argument("--layer-decay", type=float, default=1.0, metavar="X",
+                   help="layer-wise LR decay, X in (0, 1]: the heads train "
+                        "at the scheduled rate, each layer below at X times "
+                        "the one above; final fine-tune stage only, not "
+                        "--mlm or --pretrain (1 = off)")
     p.set_defaults(fn=cmd_train)
 
     args = ap.parse_args(argv)

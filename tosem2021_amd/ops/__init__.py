@@ -821,3 +821,99 @@ def adamw_step_clipped(p, grad, m, v, master, *, lr, beta1=0.9, beta2=0.999,
     else:
         reference.adamw_step_clipped(p, grad, m, v, master, lr, beta1, beta2,
                                      eps, wd, step, clip_state)
+
+
+MAX_SEGMENTS = 1024     # AD_MAX_SEGS of csrc/adamw.hip: the table's LDS image
+
+
+def check_segment_table(seg_end, seg_lr_mult, seg_wd, n):
+    """Validate a HOST segment table (sequences or CPU tensors) for a flat
+    buffer of n elements: one length 1 <= S <= MAX_SEGMENTS, seg_end
+    strictly increasing from above 0 and ending at n."""
+    ends = [int(e) for e in seg_end]
+    S = len(ends)
+    if not (len(seg_lr_mult) == len(seg_wd) == S):
+        raise ValueError("seg_end, seg_lr_mult and seg_wd must have one "
+                         f"length, got {S}, {len(seg_lr_mult)}, "
+                         f"{len(seg_wd)}")
+    if not 1 <= S <= MAX_SEGMENTS:
+        raise ValueError(f"the segment table holds 1 to {MAX_SEGMENTS} "
+                         f"segments, got {S}")
+    if ends[0] <= 0 or any(b <= a for a, b in zip(ends, ends[1:])):
+        raise ValueError("seg_end must be strictly increasing from above 0")
+    if ends[-1] != n:
+        raise ValueError(f"the last segment must end at n = {n}, got "
+                         f"{ends[-1]}")
+
+
+def segment_table(seg_end, seg_lr_mult, seg_wd, n, device=None):
+    """Check a host segment table (check_segment_table) and upload it:
+    (seg_end int64, seg_lr_mult f32, seg_wd f32) on `device`, the operands of
+    adamw_step_grouped.  Build it once; the step itself reads nothing back."""
+    check_segment_table(seg_end, seg_lr_mult, seg_wd, n)
+    return (torch.tensor([int(e) for e in seg_end], dtype=torch.int64,
+                         device=device),
+            torch.tensor([float(x) for x in seg_lr_mult],
+                         dtype=torch.float32, device=device),
+            torch.tensor([float(x) for x in seg_wd], dtype=torch.float32,
+                         device=device))
+
+
+def _check_grouped_operands(p, seg_end, seg_lr_mult, seg_wd):
+    """What can be checked without reading a device table back: dtypes,
+    shapes, placement.  A CPU table is checked in full."""
+    if seg_end.dtype != torch.int64:
+        raise ValueError(f"seg_end must be int64, got {seg_end.dtype}")
+    for name, t in (("seg_lr_mult", seg_lr_mult), ("seg_wd", seg_wd)):
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be f32, got {t.dtype}")
+    for name, t in (("seg_end", seg_end), ("seg_lr_mult", seg_lr_mult),
+                    ("seg_wd", seg_wd)):
+        if t.dim() != 1 or not t.is_contiguous() or t.device != p.device:
+            raise ValueError(f"{name} must be 1-D, contiguous and on "
+                             f"{p.device}")
+    S = seg_end.numel()
+    if not (seg_lr_mult.numel() == seg_wd.numel() == S):
+        raise ValueError("seg_end, seg_lr_mult and seg_wd must have one "
+                         "length")
+    if not 1 <= S <= MAX_SEGMENTS:
+        raise ValueError(f"the segment table holds 1 to {MAX_SEGMENTS} "
+                         f"segments, got {S}")
+    if not p.is_cuda:
+        check_segment_table(seg_end.tolist(), seg_lr_mult, seg_wd, p.numel())
+
+
+def adamw_step_grouped(p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd,
+                       *, lr, beta1=0.9, beta2=0.999, eps=1e-8, step,
+                       grad_scale=1.0):
+    """adamw_step with parameter groups over the flat buffer: element e
+    belongs to the first segment s with e < seg_end[s] and steps at
+    lr * seg_lr_mult[s] (an f32 product) with weight decay seg_wd[s], bit for
+    bit what adamw_step computes with those two scalars.  The table comes
+    from segment_table(), which checks its values on the host; on the GPU
+    nothing is read back here."""
+    _check_grouped_operands(p, seg_end, seg_lr_mult, seg_wd)
+    if p.is_cuda:
+        hip_ops().adamw_step_grouped(p, grad, m, v, master, seg_end,
+                                     seg_lr_mult, seg_wd, lr, beta1, beta2,
+                                     eps, step, grad_scale)
+    else:
+        reference.adamw_step_grouped(p, grad, m, v, master, seg_end,
+                                     seg_lr_mult, seg_wd, lr, beta1, beta2,
+                                     eps, step, grad_scale)
+
+
+def adamw_step_grouped_clipped(p, grad, m, v, master, seg_end, seg_lr_mult,
+                               seg_wd, *, lr, beta1=0.9, beta2=0.999,
+                               eps=1e-8, step, clip_state):
+    """adamw_step_grouped with the grad scale and the skip flag read on the
+    device from grad_clip_state's result, as adamw_step_clipped."""
+    _check_grouped_operands(p, seg_end, seg_lr_mult, seg_wd)
+    if p.is_cuda:
+        hip_ops().adamw_step_grouped_clipped(
+            p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd, lr, beta1,
+            beta2, eps, step, clip_state)
+    else:
+        reference.adamw_step_grouped_clipped(
+            p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd, lr, beta1,
+            beta2, eps, step, clip_state)

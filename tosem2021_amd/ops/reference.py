@@ -266,6 +266,13 @@ def adamw_step(
     step: int,
     grad_scale: float = 1.0,
 ) -> None:
+    _adamw_update(p, grad, m, v, master, lr, beta1, beta2, eps, wd, step,
+                  grad_scale)
+
+
+def _adamw_update(p, grad, m, v, master, lr, beta1, beta2, eps, wd, step,
+                  grad_scale):
+    """The AdamW arithmetic; lr and wd are floats or per-element f32 tensors."""
     g = grad.float() * grad_scale
     m.mul_(beta1).add_(g, alpha=1 - beta1)
     v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
@@ -275,6 +282,23 @@ def adamw_step(
     vhat = v * bc2
     master.add_(-(lr * (mhat / (vhat.sqrt() + eps) + wd * master)))
     p.copy_(master.to(p.dtype))
+
+
+def adamw_step_grouped(p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd,
+                       lr, beta1, beta2, eps, step, grad_scale=1.0) -> None:
+    """adamw_step with parameter groups over the flat buffer
+    (csrc/adamw.hip): seg_end int64 [S] holds strictly increasing exclusive
+    end offsets with seg_end[-1] == n, and the elements of segment s step at
+    lr * seg_lr_mult[s], an f32 product as in the kernel, with weight decay
+    seg_wd[s]."""
+    f32 = torch.float32
+    lens = torch.diff(seg_end, prepend=seg_end.new_zeros(1))
+    lr_s = torch.tensor(lr, dtype=f32, device=master.device) \
+        * seg_lr_mult.to(f32)
+    lr_e = torch.repeat_interleave(lr_s, lens)
+    wd_e = torch.repeat_interleave(seg_wd.to(f32), lens)
+    _adamw_update(p, grad, m, v, master, lr_e, beta1, beta2, eps, wd_e, step,
+                  grad_scale)
 
 
 def grad_clip_state(grad: torch.Tensor, grad_scale: float,
@@ -305,6 +329,18 @@ def adamw_step_clipped(p, grad, m, v, master, lr, beta1, beta2, eps, wd,
         return
     adamw_step(p, grad, m, v, master, lr, beta1, beta2, eps, wd, step,
                grad_scale=float(clip_state[1]))
+
+
+def adamw_step_grouped_clipped(p, grad, m, v, master, seg_end, seg_lr_mult,
+                               seg_wd, lr, beta1, beta2, eps, step,
+                               clip_state) -> None:
+    """adamw_step_grouped at the clipped grad scale; a non-finite gradient
+    (clip_state[2] == 0) leaves every buffer untouched."""
+    if float(clip_state[2]) == 0.0:
+        return
+    adamw_step_grouped(p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd,
+                       lr, beta1, beta2, eps, step,
+                       grad_scale=float(clip_state[1]))
 
 
 def dead_q_tiles(dout: torch.Tensor, n_heads: Optional[int] = None

@@ -63,6 +63,47 @@ class FlatParams:
         self.grad_flat.zero_()
 
 
+def param_depth(name: str, n_layers: int) -> int:
+    """Layer-wise LR decay depth of a parameter by its name: the embeddings
+    0, blocks.i.* i + 1, everything above the blocks (ln_f, heads.*)
+    n_layers + 1."""
+    if name.startswith(("tok_emb.", "pos_emb.")):
+        return 0
+    if name.startswith("blocks."):
+        return int(name.split(".")[1]) + 1
+    return n_layers + 1
+
+
+def param_group_table(model: torch.nn.Module, n_layers: int, padded: int, *,
+                      weight_decay: float, no_decay_1d: bool = False,
+                      layer_decay: float = 1.0):
+    """The segment table of ops.adamw_step_grouped for `model`'s parameters
+    in FlatParams' order, as host lists (seg_end, seg_lr_mult, seg_wd).
+
+    A parameter gets lr_mult = layer_decay ** (n_layers + 1 - depth)
+    (param_depth) and wd = 0 if no_decay_1d and it is 1-D, else weight_decay.
+    Neighbours with equal (lr_mult, wd) share a segment, and the padding
+    tail up to `padded` joins the last one."""
+    ends: List[int] = []
+    mults: List[float] = []
+    wds: List[float] = []
+    off = 0
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        off += p.numel()
+        mult = float(layer_decay) ** (n_layers + 1 - param_depth(name, n_layers))
+        wd = 0.0 if no_decay_1d and p.dim() == 1 else float(weight_decay)
+        if ends and (mults[-1], wds[-1]) == (mult, wd):
+            ends[-1] = off
+        else:
+            ends.append(off)
+            mults.append(mult)
+            wds.append(wd)
+    ends[-1] = padded
+    return ends, mults, wds
+
+
 @dataclass
 class TrainConfig:
     model: str = "mltc-base"
@@ -80,6 +121,15 @@ class TrainConfig:
     ckpt_keep: int = 3           # retain the newest k checkpoints (0 = all)
     # global-norm gradient clipping + non-finite step skipping; 0 = off
     max_grad_norm: float = 0.0
+    # parameter groups inside the fused AdamW step (param_group_table); with
+    # both at their defaults the step is the ungrouped kernel
+    no_decay_1d: bool = False    # no weight decay on 1-D parameters
+    layer_decay: float = 1.0     # layer-wise LR decay factor, in (0, 1]
+
+    def __post_init__(self):
+        if not 0.0 < self.layer_decay <= 1.0:
+            raise ValueError(
+                f"layer_decay must be in (0, 1], got {self.layer_decay}")
 
 
 class Trainer:
@@ -107,6 +157,17 @@ class Trainer:
         self.skipped_steps = 0
         self.metrics: Dict[str, float] = {}
         self._clip_state: Optional[torch.Tensor] = None
+        # parameter groups: a function of the config alone, so every rank
+        # and a resumed run derive the same table; uploaded once
+        self._seg_table = None
+        if cfg.no_decay_1d or cfg.layer_decay != 1.0:
+            self._seg_table = ops.segment_table(
+                *param_group_table(self.model, self.model.cfg.n_layers,
+                                   self.flat.padded,
+                                   weight_decay=cfg.weight_decay,
+                                   no_decay_1d=cfg.no_decay_1d,
+                                   layer_decay=cfg.layer_decay),
+                self.flat.padded, device=self.device)
 
     # ---- schedule -----------------------------------------------------------
     def _lr(self) -> float:
@@ -131,18 +192,33 @@ class Trainer:
         is reduced on the device (ops.grad_clip_state) and the clip factor
         folds into the kernel's grad scale; a non-finite gradient makes the
         kernel leave every buffer untouched.  _finish_step() reads the
-        outcome back where the step syncs anyway."""
+        outcome back where the step syncs anyway.
+
+        With cfg.no_decay_1d or cfg.layer_decay != 1 the same step runs
+        through the grouped entry points: lr is still the scheduled base
+        rate, and the per-segment multiplier and weight decay come from the
+        table built at construction.  The norm and the clip are global
+        either way."""
         f, c = self.flat, self.cfg
         hp = dict(lr=lr, beta1=c.beta1, beta2=c.beta2, eps=c.eps,
-                  wd=c.weight_decay, step=self.opt_step + 1)
+                  step=self.opt_step + 1)
+        bufs = (f.flat, f.grad_flat, f.m, f.v, f.master)
         if c.max_grad_norm > 0:
             self._clip_state = ops.grad_clip_state(
                 f.grad_flat, grad_scale=grad_scale, max_norm=c.max_grad_norm)
-            ops.adamw_step_clipped(f.flat, f.grad_flat, f.m, f.v, f.master,
-                                   clip_state=self._clip_state, **hp)
+            if self._seg_table is not None:
+                ops.adamw_step_grouped_clipped(
+                    *bufs, *self._seg_table, clip_state=self._clip_state,
+                    **hp)
+            else:
+                ops.adamw_step_clipped(*bufs, clip_state=self._clip_state,
+                                       wd=c.weight_decay, **hp)
+        elif self._seg_table is not None:
+            ops.adamw_step_grouped(*bufs, *self._seg_table,
+                                   grad_scale=grad_scale, **hp)
         else:
-            ops.adamw_step(f.flat, f.grad_flat, f.m, f.v, f.master,
-                           grad_scale=grad_scale, **hp)
+            ops.adamw_step(*bufs, grad_scale=grad_scale,
+                           wd=c.weight_decay, **hp)
 
     def _finish_step(self) -> dict:
         """Count the step as applied or skipped; returns the extra

@@ -45,6 +45,7 @@ def load_config(path: str) -> ExperimentConfig:
         base = CONFIGS.get(model_name or "mltc-base", CONFIGS["mltc-base"])
         cfg.model_cfg = MLTCConfig(**{**base.__dict__, **data.pop("model_cfg")})
     _apply(cfg, data, "")
+    cfg.train.__post_init__()   # the keys were set past the constructor
     return cfg
 
 
