@@ -116,6 +116,35 @@ hipError_t adamw_grouped_clipped_launch(
     int step, const void* seg_end, const void* seg_lr_mult,
     const void* seg_wd, int n_seg, const void* clip_state,
     hipStream_t stream);
+// The EMA forms of the four: ema [n] f32 (not nullptr, hipErrorInvalidValue
+// otherwise), the same flat layout as master, becomes
+// ema_decay * ema + (1.f - ema_decay) * w with w the new master value: two f32
+// products and one f32 sum, never fused.  p_bf16, m, v and master come out as
+// from the launcher without _ema; a skipped step leaves ema untouched too.
+hipError_t adamw_ema_launch(void* p_bf16, const void* grad, int grad_is_f32,
+                            void* m, void* v, void* master, void* ema,
+                            float ema_decay, long n, float lr, float beta1,
+                            float beta2, float eps, float wd, int step,
+                            float grad_scale, hipStream_t stream);
+hipError_t adamw_clipped_ema_launch(void* p_bf16, const void* grad,
+                                    int grad_is_f32, void* m, void* v,
+                                    void* master, void* ema, float ema_decay,
+                                    long n, float lr, float beta1,
+                                    float beta2, float eps, float wd, int step,
+                                    const void* clip_state,
+                                    hipStream_t stream);
+hipError_t adamw_grouped_ema_launch(
+    void* p_bf16, const void* grad, int grad_is_f32, void* m, void* v,
+    void* master, void* ema, float ema_decay, long n, float lr, float beta1,
+    float beta2, float eps, int step, const void* seg_end,
+    const void* seg_lr_mult, const void* seg_wd, int n_seg, float grad_scale,
+    hipStream_t stream);
+hipError_t adamw_grouped_clipped_ema_launch(
+    void* p_bf16, const void* grad, int grad_is_f32, void* m, void* v,
+    void* master, void* ema, float ema_decay, long n, float lr, float beta1,
+    float beta2, float eps, int step, const void* seg_end,
+    const void* seg_lr_mult, const void* seg_wd, int n_seg,
+    const void* clip_state, hipStream_t stream);
 // partials is [grad_norm_grid(n)] f32; n % 8 == 0.
 hipError_t grad_clip_state_launch(const void* grad, int grad_is_f32, long n,
                                   float grad_scale, float max_norm,

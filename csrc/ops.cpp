@@ -414,10 +414,24 @@ torch::Tensor softmax_bwd(torch::Tensor dp, torch::Tensor p, double scale) {
   return ds;
 }
 
+// The weight average of the EMA forms of the AdamW step: f32 [n], contiguous,
+// 16-byte aligned (16 B per lane loads), on p's device; 0 <= decay < 1.
+void check_ema(const torch::Tensor& ema, const torch::Tensor& p,
+               double ema_decay) {
+  check_f32(ema, "ema");
+  TORCH_CHECK(ema.numel() == p.numel(), "ema must have p's length");
+  TORCH_CHECK(ema.device() == p.device(), "ema must be on p's device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(ema.data_ptr()) % 16 == 0,
+              "ema must be 16-byte aligned");
+  TORCH_CHECK(ema_decay >= 0.0 && ema_decay < 1.0,
+              "ema_decay must be in [0, 1), got ", ema_decay);
+}
+
 void adamw_step(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
                 torch::Tensor v, torch::Tensor master, double lr, double beta1,
                 double beta2, double eps, double wd, long step,
-                double grad_scale) {
+                double grad_scale, c10::optional<torch::Tensor> ema,
+                double ema_decay) {
   check_bf16(p, "p"); check_f32(m, "m"); check_f32(v, "v");
   check_f32(master, "master");
   TORCH_CHECK(grad.is_contiguous() && grad.device().is_cuda(), "bad grad");
@@ -428,6 +442,15 @@ void adamw_step(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
   TORCH_CHECK(n % 4 == 0, "flat parameter buffer must be padded to 4 elems");
   TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n &&
               master.numel() == n, "size mismatch");
+  if (ema.has_value()) {
+    check_ema(*ema, p, ema_decay);
+    CHECK_HIP(adamw_ema_launch(
+        p.data_ptr(), grad.data_ptr(), gf32, m.data_ptr(), v.data_ptr(),
+        master.data_ptr(), ema->data_ptr(), (float)ema_decay, n, (float)lr,
+        (float)beta1, (float)beta2, (float)eps, (float)wd, (int)step,
+        (float)grad_scale, cur_stream()));
+    return;
+  }
   CHECK_HIP(adamw_launch(p.data_ptr(), grad.data_ptr(), gf32, m.data_ptr(),
                          v.data_ptr(), master.data_ptr(), n, (float)lr,
                          (float)beta1, (float)beta2, (float)eps, (float)wd,
@@ -469,7 +492,8 @@ torch::Tensor grad_clip_state(torch::Tensor grad, double grad_scale,
 void adamw_step_clipped(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
                         torch::Tensor v, torch::Tensor master, double lr,
                         double beta1, double beta2, double eps, double wd,
-                        long step, torch::Tensor clip_state) {
+                        long step, torch::Tensor clip_state,
+                        c10::optional<torch::Tensor> ema, double ema_decay) {
   check_bf16(p, "p"); check_f32(m, "m"); check_f32(v, "v");
   check_f32(master, "master"); check_f32(clip_state, "clip_state");
   int gf32 = check_flat_grad(grad);
@@ -477,6 +501,15 @@ void adamw_step_clipped(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
   const long n = p.numel();
   TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n &&
               master.numel() == n, "size mismatch");
+  if (ema.has_value()) {
+    check_ema(*ema, p, ema_decay);
+    CHECK_HIP(adamw_clipped_ema_launch(
+        p.data_ptr(), grad.data_ptr(), gf32, m.data_ptr(), v.data_ptr(),
+        master.data_ptr(), ema->data_ptr(), (float)ema_decay, n, (float)lr,
+        (float)beta1, (float)beta2, (float)eps, (float)wd, (int)step,
+        clip_state.data_ptr(), cur_stream()));
+    return;
+  }
   CHECK_HIP(adamw_clipped_launch(p.data_ptr(), grad.data_ptr(), gf32,
                                  m.data_ptr(), v.data_ptr(),
                                  master.data_ptr(), n, (float)lr,
@@ -510,7 +543,8 @@ void adamw_step_grouped(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
                         torch::Tensor seg_end, torch::Tensor seg_lr_mult,
                         torch::Tensor seg_wd, double lr, double beta1,
                         double beta2, double eps, long step,
-                        double grad_scale) {
+                        double grad_scale, c10::optional<torch::Tensor> ema,
+                        double ema_decay) {
   check_bf16(p, "p"); check_f32(m, "m"); check_f32(v, "v");
   check_f32(master, "master");
   TORCH_CHECK(grad.is_contiguous() && grad.device().is_cuda(), "bad grad");
@@ -522,6 +556,16 @@ void adamw_step_grouped(torch::Tensor p, torch::Tensor grad, torch::Tensor m,
   TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n &&
               master.numel() == n, "size mismatch");
   int S = check_segment_table(seg_end, seg_lr_mult, seg_wd);
+  if (ema.has_value()) {
+    check_ema(*ema, p, ema_decay);
+    CHECK_HIP(adamw_grouped_ema_launch(
+        p.data_ptr(), grad.data_ptr(), gf32, m.data_ptr(), v.data_ptr(),
+        master.data_ptr(), ema->data_ptr(), (float)ema_decay, n, (float)lr,
+        (float)beta1, (float)beta2, (float)eps, (int)step, seg_end.data_ptr(),
+        seg_lr_mult.data_ptr(), seg_wd.data_ptr(), S, (float)grad_scale,
+        cur_stream()));
+    return;
+  }
   CHECK_HIP(adamw_grouped_launch(
       p.data_ptr(), grad.data_ptr(), gf32, m.data_ptr(), v.data_ptr(),
       master.data_ptr(), n, (float)lr, (float)beta1, (float)beta2, (float)eps,
@@ -535,7 +579,9 @@ void adamw_step_grouped_clipped(torch::Tensor p, torch::Tensor grad,
                                 torch::Tensor seg_lr_mult,
                                 torch::Tensor seg_wd, double lr, double beta1,
                                 double beta2, double eps, long step,
-                                torch::Tensor clip_state) {
+                                torch::Tensor clip_state,
+                                c10::optional<torch::Tensor> ema,
+                                double ema_decay) {
   check_bf16(p, "p"); check_f32(m, "m"); check_f32(v, "v");
   check_f32(master, "master"); check_f32(clip_state, "clip_state");
   int gf32 = check_flat_grad(grad);
@@ -544,6 +590,16 @@ void adamw_step_grouped_clipped(torch::Tensor p, torch::Tensor grad,
   TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n &&
               master.numel() == n, "size mismatch");
   int S = check_segment_table(seg_end, seg_lr_mult, seg_wd);
+  if (ema.has_value()) {
+    check_ema(*ema, p, ema_decay);
+    CHECK_HIP(adamw_grouped_clipped_ema_launch(
+        p.data_ptr(), grad.data_ptr(), gf32, m.data_ptr(), v.data_ptr(),
+        master.data_ptr(), ema->data_ptr(), (float)ema_decay, n, (float)lr,
+        (float)beta1, (float)beta2, (float)eps, (int)step, seg_end.data_ptr(),
+        seg_lr_mult.data_ptr(), seg_wd.data_ptr(), S, clip_state.data_ptr(),
+        cur_stream()));
+    return;
+  }
   CHECK_HIP(adamw_grouped_clipped_launch(
       p.data_ptr(), grad.data_ptr(), gf32, m.data_ptr(), v.data_ptr(),
       master.data_ptr(), n, (float)lr, (float)beta1, (float)beta2, (float)eps,
@@ -1180,7 +1236,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_bf16") = false);
   m.def("softmax_fwd", &softmax_fwd, "fused scaled masked softmax fwd");
   m.def("softmax_bwd", &softmax_bwd, "fused softmax bwd");
-  m.def("adamw_step", &adamw_step, "fused AdamW over flat params");
+  // ema (None = off): the f32 weight average the EMA kernels keep
+  m.def("adamw_step", &adamw_step, "fused AdamW over flat params",
+        py::arg("p"), py::arg("grad"), py::arg("m"), py::arg("v"),
+        py::arg("master"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("wd"), py::arg("step"), py::arg("grad_scale"),
+        py::arg("ema") = py::none(), py::arg("ema_decay") = 0.0);
   m.def("grad_clip_state", &grad_clip_state,
         "deterministic global grad norm -> device {norm, scale, finite, "
         "sumsq}");
@@ -1194,10 +1255,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("logits"), py::arg("target"), py::arg("lse"),
         py::arg("grow"), py::arg("ignore_index") = -100);
   m.def("adamw_step_clipped", &adamw_step_clipped,
-        "fused AdamW reading its grad scale / skip flag from clip_state");
+        "fused AdamW reading its grad scale / skip flag from clip_state",
+        py::arg("p"), py::arg("grad"), py::arg("m"), py::arg("v"),
+        py::arg("master"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("wd"), py::arg("step"), py::arg("clip_state"),
+        py::arg("ema") = py::none(), py::arg("ema_decay") = 0.0);
   m.def("adamw_step_grouped", &adamw_step_grouped,
-        "fused AdamW with per-segment lr multiplier and weight decay");
+        "fused AdamW with per-segment lr multiplier and weight decay",
+        py::arg("p"), py::arg("grad"), py::arg("m"), py::arg("v"),
+        py::arg("master"), py::arg("seg_end"), py::arg("seg_lr_mult"),
+        py::arg("seg_wd"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("step"), py::arg("grad_scale"),
+        py::arg("ema") = py::none(), py::arg("ema_decay") = 0.0);
   m.def("adamw_step_grouped_clipped", &adamw_step_grouped_clipped,
         "adamw_step_grouped reading its grad scale / skip flag from "
-        "clip_state");
+        "clip_state",
+        py::arg("p"), py::arg("grad"), py::arg("m"), py::arg("v"),
+        py::arg("master"), py::arg("seg_end"), py::arg("seg_lr_mult"),
+        py::arg("seg_wd"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("step"), py::arg("clip_state"),
+        py::arg("ema") = py::none(), py::arg("ema_decay") = 0.0);
 }

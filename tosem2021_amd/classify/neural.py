@@ -255,7 +255,8 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                      mlm_prob: float = 0.15,
                      weight_decay: float = 0.01,
                      no_decay_1d: bool = False,
-                     layer_decay: float = 1.0) -> dict:
+                     layer_decay: float = 1.0,
+                     ema_decay: float = 0.0) -> dict:
     """Fine-tune MLTC on `taxonomy_path`'s labeled rows.
 
     `fused_dropout` runs the residual dropout inside the add+LayerNorm
@@ -280,6 +281,14 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
     the one above.  It applies to the final fine-tune stage only; the MLM
     and supervised pretraining stages train from scratch, where a smaller
     rate at the bottom only slows them.
+
+    `ema_decay` in [0, 1), 0 = off, keeps an exponential moving average of
+    the fine-tune stage's weights inside the fused AdamW step
+    (TrainConfig.ema_decay), seeded from the weights that stage starts from.
+    The result's usual keys still report the raw weights; the same
+    evaluation under Trainer.ema_weights() is reported with an `ema_` prefix,
+    `dump_probs_path` also gets `ema_val_probs` and `ema_train_probs`, and
+    the checkpoint carries the average for `apply_classifier(use_ema=True)`.
 
     `pack` trains and evaluates on packed batches (data.packing): each
     step's `batch` examples share rows of `seq` tokens instead of one padded
@@ -319,7 +328,8 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
                        total_steps=steps, ckpt_dir=ckpt_dir,
                        dtype="bf16" if dev.type == "cuda" else "f32",
                        max_grad_norm=max_grad_norm, weight_decay=weight_decay,
-                       no_decay_1d=no_decay_1d, layer_decay=layer_decay)
+                       no_decay_1d=no_decay_1d, layer_decay=layer_decay,
+                       ema_decay=ema_decay)
     trainer = Trainer(tcfg, device=dev, model_cfg=cfg)
     trainer.model.set_pos_weights(
         {k: v.to(dev) for k, v in train_ds.pos_weights().items()})
@@ -379,27 +389,50 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
         trainer.flat.master.copy_(pre_tr.flat.master)
         del pre_tr
         pretrain_time = time.time() - t0
+    if ema_decay > 0 and trainer.step_num == 0:
+        # the average starts from the warm-started weights, not from the
+        # random ones the trainer was built with
+        trainer.reset_ema()
 
     losses, epoch = _run_steps(trainer, train_ds, tok, batch, seq, steps,
                                seed, dev, eval_every, val_ds,
                                augment=augment, pack=pack)
     train_time = time.time() - t0
-    ev = evaluate(trainer, val_ds, tok, seq, pack=pack)
-    ev_lo = evaluate(trainer, val_ds, tok, seq, threshold=0.3, pack=pack)
-    ev["strategy_micro_f1_t0.3"] = ev_lo["strategy_micro_f1"]
-    ev["property_micro_f1_t0.3"] = ev_lo["property_micro_f1"]
-    ths = tune_thresholds(trainer, train_ds, tok, seq, pack=pack)
-    ev_tuned = evaluate(trainer, val_ds, tok, seq, thresholds=ths, pack=pack)
-    ev["strategy_micro_f1_tuned"] = round(ev_tuned["strategy_micro_f1"], 4)
-    ev["property_micro_f1_tuned"] = round(ev_tuned["property_micro_f1"], 4)
-    if dump_probs_path:
-        # sigmoid probs + gold for the val AND train splits — enables
-        # offline ensembling/blending without the GPU
-        vp, vg = _head_probs(trainer, val_ds, tok, seq, pack=pack)
-        tp_, tg = _head_probs(trainer, train_ds, tok, seq, pack=pack)
-        torch.save({"val_probs": vp, "val_gold": vg,
-                    "train_probs": tp_, "train_gold": tg,
-                    "seed": seed}, dump_probs_path)
+
+    def eval_block():
+        ev = evaluate(trainer, val_ds, tok, seq, pack=pack)
+        ev_lo = evaluate(trainer, val_ds, tok, seq, threshold=0.3, pack=pack)
+        ev["strategy_micro_f1_t0.3"] = ev_lo["strategy_micro_f1"]
+        ev["property_micro_f1_t0.3"] = ev_lo["property_micro_f1"]
+        ths = tune_thresholds(trainer, train_ds, tok, seq, pack=pack)
+        ev_tuned = evaluate(trainer, val_ds, tok, seq, thresholds=ths,
+                            pack=pack)
+        ev["strategy_micro_f1_tuned"] = round(
+            ev_tuned["strategy_micro_f1"], 4)
+        ev["property_micro_f1_tuned"] = round(
+            ev_tuned["property_micro_f1"], 4)
+        probs = None
+        if dump_probs_path:
+            # sigmoid probs + gold for the val AND train splits — enables
+            # offline ensembling/blending without the GPU
+            vp, vg = _head_probs(trainer, val_ds, tok, seq, pack=pack)
+            tp_, tg = _head_probs(trainer, train_ds, tok, seq, pack=pack)
+            probs = {"val_probs": vp, "val_gold": vg,
+                     "train_probs": tp_, "train_gold": tg}
+        return ev, probs
+
+    ev, probs = eval_block()
+    if ema_decay > 0:
+        # the same block on the averaged weights; the raw ones come back bit
+        # for bit before the checkpoint is written
+        with trainer.ema_weights():
+            ema_ev, ema_probs = eval_block()
+        ev.update({f"ema_{k}": v for k, v in ema_ev.items()})
+        if probs is not None:
+            probs["ema_val_probs"] = ema_probs["val_probs"]
+            probs["ema_train_probs"] = ema_probs["train_probs"]
+    if probs is not None:
+        torch.save({**probs, "seed": seed}, dump_probs_path)
     if ckpt_dir:
         trainer.save()
     clip = {}
@@ -422,16 +455,31 @@ def train_classifier(taxonomy_path: str, model: str = "mltc-base",
     }
 
 
+def load_ema_weights(trainer: Trainer, ckpt_path: str) -> None:
+    """Put the weight average saved in `ckpt_path` into the weights of
+    `trainer`'s model, cast to their dtype: inference with a trainer that
+    itself keeps no average."""
+    sd = torch.load(ckpt_path, map_location=trainer.device, weights_only=True)
+    if "ema" not in sd:
+        raise ValueError(
+            f"checkpoint {ckpt_path} holds no weight average (\"ema\"): it "
+            "was not trained with ema_decay > 0")
+    trainer.flat.flat.copy_(sd["ema"])
+
+
 @torch.no_grad()
 def apply_classifier(ckpt_dir: str, taxonomy_path: str, out_csv: str,
                      model: str = "mltc-base", seq: int = 256,
                      batch: int = 64, threshold: float = 0.5,
                      device: Optional[str] = None,
-                     repo_prefix: bool = False, pack: bool = False) -> str:
+                     repo_prefix: bool = False, pack: bool = False,
+                     use_ema: bool = False) -> str:
     """Label the rows of a (mined) taxonomy CSV with a trained MLTC model and
     rewrite the 41-column CSV with the predicted labels.  `pack` runs each
     chunk of `batch` texts as one packed batch; the rows come out in input
-    order either way."""
+    order either way.  `use_ema` labels with the weight average that a run
+    with `ema_decay` > 0 saved next to the raw weights; a checkpoint without
+    one is a ValueError."""
     from tosem2021_amd.extract.schema import (
         METHODS, PROPERTIES, STAGES, STRATEGIES, STRATEGY_TO_COLUMNS,
         TestCaseRow)
@@ -448,6 +496,8 @@ def apply_classifier(ckpt_dir: str, taxonomy_path: str, out_csv: str,
                        dtype="bf16" if dev.type == "cuda" else "f32")
     trainer = Trainer(tcfg, device=dev, model_cfg=cfg)
     assert trainer.load_or_init(), f"no checkpoint found in {ckpt_dir}"
+    if use_ema:
+        load_ema_weights(trainer, Trainer.latest_checkpoint(ckpt_dir))
     trainer.model.eval()
 
     texts = (df["Labels"].astype(str) + " | " +

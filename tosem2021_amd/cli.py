@@ -128,7 +128,8 @@ def cmd_classify(args):
     out = apply_classifier(args.ckpt_dir, args.taxonomy, args.out,
                            model=args.model, seq=args.seq,
                            threshold=args.threshold,
-                           repo_prefix=args.repo_prefix, pack=args.pack)
+                           repo_prefix=args.repo_prefix, pack=args.pack,
+                           use_ema=args.ema)
     print(f"wrote {out}")
 
 
@@ -147,7 +148,7 @@ def cmd_train(args):
         max_grad_norm=args.clip_grad_norm, mlm_path=args.mlm,
         mlm_steps=args.mlm_steps, mlm_prob=args.mlm_prob,
         weight_decay=args.weight_decay, no_decay_1d=args.no_decay_1d,
-        layer_decay=args.layer_decay)
+        layer_decay=args.layer_decay, ema_decay=args.ema_decay)
     print(json.dumps(res, indent=2))
 
 
@@ -231,6 +232,9 @@ def main(argv=None):
     p.add_argument("--pack", action="store_true",
                    help="pack several texts per row instead of padding "
                         "each to its own row")
+    p.add_argument("--ema", action="store_true",
+                   help="label with the weight average of a checkpoint "
+                        "trained with --ema-decay")
     p.set_defaults(fn=cmd_classify)
 
     p = sub.add_parser("train", help="train the MLTC classifier on a taxonomy")
@@ -290,6 +294,11 @@ def main(argv=None):
                         "at the scheduled rate, each layer below at X times "
                         "the one above; final fine-tune stage only, not "
                         "--mlm or --pretrain (1 = off)")
+    p.add_argument("--ema-decay", type=_rate, default=0.0, metavar="X",
+                   help="exponential moving average of the weights inside "
+                        "the fused AdamW step, X in [0, 1): also evaluated "
+                        "(ema_ keys) and saved for classify --ema; final "
+                        "fine-tune stage only (0 = off)")
     p.set_defaults(fn=cmd_train)
 
     args = ap.parse_args(argv)

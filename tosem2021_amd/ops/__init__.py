@@ -786,10 +786,50 @@ def fused_cross_entropy(logits, target, ignore_index: int = -100):
     return _CrossEntropyFn.apply(logits, target, ignore_index)
 
 
+def _check_ema(p, ema, ema_decay):
+    """The weight-average operands of the four AdamW steps: both None (off),
+    or ema f32, contiguous, of p's length and on p's device with
+    0 <= ema_decay < 1.  Returns whether the average is on."""
+    if ema is None and ema_decay is None:
+        return False
+    if ema is None or ema_decay is None:
+        raise ValueError("ema and ema_decay go together: got "
+                         f"ema={'None' if ema is None else 'a tensor'}, "
+                         f"ema_decay={ema_decay}")
+    if ema.dtype != torch.float32:
+        raise ValueError(f"ema must be f32, got {ema.dtype}")
+    if ema.dim() != 1 or not ema.is_contiguous():
+        raise ValueError("ema must be 1-D and contiguous")
+    if ema.numel() != p.numel():
+        raise ValueError(f"ema must have p's length {p.numel()}, got "
+                         f"{ema.numel()}")
+    if ema.device != p.device:
+        raise ValueError(f"ema must be on {p.device}, got {ema.device}")
+    if ema.is_cuda and ema.data_ptr() % 16:
+        raise ValueError("ema on the GPU must be 16-byte aligned")
+    if not 0.0 <= ema_decay < 1.0:
+        raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay}")
+    return True
+
+
 def adamw_step(p, grad, m, v, master, *, lr, beta1=0.9, beta2=0.999, eps=1e-8,
-               wd=0.01, step, grad_scale=1.0):
-    """Fused AdamW over the flat parameter buffer (see train.py)."""
-    if p.is_cuda:
+               wd=0.01, step, grad_scale=1.0, ema=None, ema_decay=None):
+    """Fused AdamW over the flat parameter buffer (see train.py).
+
+    With ema (f32, p's length) and ema_decay = d the same kernel pass also
+    keeps a weight average, ema = d * ema + (1 - d) * w with w the new f32
+    master value: two f32 products and one f32 sum, never fused, so separate
+    f32 torch ops reproduce it bit for bit.  p, m, v and master come out as
+    without it.  The other three steps take the same two operands."""
+    if _check_ema(p, ema, ema_decay):
+        if p.is_cuda:
+            hip_ops().adamw_step(p, grad, m, v, master, lr, beta1, beta2, eps,
+                                 wd, step, grad_scale, ema, ema_decay)
+        else:
+            reference.adamw_step(p, grad, m, v, master, lr, beta1, beta2, eps,
+                                 wd, step, grad_scale, ema=ema,
+                                 ema_decay=ema_decay)
+    elif p.is_cuda:
         hip_ops().adamw_step(p, grad, m, v, master, lr, beta1, beta2, eps, wd,
                              step, grad_scale)
     else:
@@ -811,11 +851,21 @@ def grad_clip_state(grad, *, grad_scale=1.0, max_norm):
 
 
 def adamw_step_clipped(p, grad, m, v, master, *, lr, beta1=0.9, beta2=0.999,
-                       eps=1e-8, wd=0.01, step, clip_state):
+                       eps=1e-8, wd=0.01, step, clip_state, ema=None,
+                       ema_decay=None):
     """adamw_step with the grad scale and the skip flag read on the device
     from grad_clip_state's result: a non-finite gradient leaves p, m, v and
-    master untouched."""
-    if p.is_cuda:
+    master untouched, and ema where it is given."""
+    if _check_ema(p, ema, ema_decay):
+        if p.is_cuda:
+            hip_ops().adamw_step_clipped(p, grad, m, v, master, lr, beta1,
+                                         beta2, eps, wd, step, clip_state,
+                                         ema, ema_decay)
+        else:
+            reference.adamw_step_clipped(p, grad, m, v, master, lr, beta1,
+                                         beta2, eps, wd, step, clip_state,
+                                         ema=ema, ema_decay=ema_decay)
+    elif p.is_cuda:
         hip_ops().adamw_step_clipped(p, grad, m, v, master, lr, beta1, beta2,
                                      eps, wd, step, clip_state)
     else:
@@ -885,7 +935,7 @@ def _check_grouped_operands(p, seg_end, seg_lr_mult, seg_wd):
 
 def adamw_step_grouped(p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd,
                        *, lr, beta1=0.9, beta2=0.999, eps=1e-8, step,
-                       grad_scale=1.0):
+                       grad_scale=1.0, ema=None, ema_decay=None):
     """adamw_step with parameter groups over the flat buffer: element e
     belongs to the first segment s with e < seg_end[s] and steps at
     lr * seg_lr_mult[s] (an f32 product) with weight decay seg_wd[s], bit for
@@ -893,7 +943,18 @@ def adamw_step_grouped(p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd,
     from segment_table(), which checks its values on the host; on the GPU
     nothing is read back here."""
     _check_grouped_operands(p, seg_end, seg_lr_mult, seg_wd)
-    if p.is_cuda:
+    if _check_ema(p, ema, ema_decay):
+        if p.is_cuda:
+            hip_ops().adamw_step_grouped(p, grad, m, v, master, seg_end,
+                                         seg_lr_mult, seg_wd, lr, beta1,
+                                         beta2, eps, step, grad_scale, ema,
+                                         ema_decay)
+        else:
+            reference.adamw_step_grouped(p, grad, m, v, master, seg_end,
+                                         seg_lr_mult, seg_wd, lr, beta1,
+                                         beta2, eps, step, grad_scale,
+                                         ema=ema, ema_decay=ema_decay)
+    elif p.is_cuda:
         hip_ops().adamw_step_grouped(p, grad, m, v, master, seg_end,
                                      seg_lr_mult, seg_wd, lr, beta1, beta2,
                                      eps, step, grad_scale)
@@ -905,11 +966,22 @@ def adamw_step_grouped(p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd,
 
 def adamw_step_grouped_clipped(p, grad, m, v, master, seg_end, seg_lr_mult,
                                seg_wd, *, lr, beta1=0.9, beta2=0.999,
-                               eps=1e-8, step, clip_state):
+                               eps=1e-8, step, clip_state, ema=None,
+                               ema_decay=None):
     """adamw_step_grouped with the grad scale and the skip flag read on the
     device from grad_clip_state's result, as adamw_step_clipped."""
     _check_grouped_operands(p, seg_end, seg_lr_mult, seg_wd)
-    if p.is_cuda:
+    if _check_ema(p, ema, ema_decay):
+        if p.is_cuda:
+            hip_ops().adamw_step_grouped_clipped(
+                p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd, lr,
+                beta1, beta2, eps, step, clip_state, ema, ema_decay)
+        else:
+            reference.adamw_step_grouped_clipped(
+                p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd, lr,
+                beta1, beta2, eps, step, clip_state, ema=ema,
+                ema_decay=ema_decay)
+    elif p.is_cuda:
         hip_ops().adamw_step_grouped_clipped(
             p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd, lr, beta1,
             beta2, eps, step, clip_state)

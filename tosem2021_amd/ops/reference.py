@@ -265,9 +265,33 @@ def adamw_step(
     wd: float,
     step: int,
     grad_scale: float = 1.0,
+    *,
+    ema: Optional[torch.Tensor] = None,
+    ema_decay: Optional[float] = None,
 ) -> None:
     _adamw_update(p, grad, m, v, master, lr, beta1, beta2, eps, wd, step,
                   grad_scale)
+    _ema_update(ema, ema_decay, master)
+
+
+def ema_decay_at(decay: float, t: int) -> float:
+    """The weight average's decay at applied update t >= 1:
+    min(decay, (1 + t) / (10 + t)).  The warm-up keeps the random initial
+    heads out of a short run's average; decay 0 stays 0."""
+    return min(decay, (1 + t) / (10 + t))
+
+
+def _ema_update(ema, ema_decay, master) -> None:
+    """ema = d * ema + (1 - d) * master as the kernel rounds it
+    (csrc/adamw.hip): d and 1 - d are f32, and the two products and the sum
+    are three separate f32 operations, never a fused multiply-add."""
+    if ema is None:
+        return
+    d = torch.tensor(ema_decay, dtype=torch.float32, device=ema.device)
+    omd = torch.ones((), dtype=torch.float32, device=ema.device) - d
+    a = ema * d
+    b = master * omd
+    ema.copy_(a + b)
 
 
 def _adamw_update(p, grad, m, v, master, lr, beta1, beta2, eps, wd, step,
@@ -285,7 +309,8 @@ def _adamw_update(p, grad, m, v, master, lr, beta1, beta2, eps, wd, step,
 
 
 def adamw_step_grouped(p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd,
-                       lr, beta1, beta2, eps, step, grad_scale=1.0) -> None:
+                       lr, beta1, beta2, eps, step, grad_scale=1.0, *,
+                       ema=None, ema_decay=None) -> None:
     """adamw_step with parameter groups over the flat buffer
     (csrc/adamw.hip): seg_end int64 [S] holds strictly increasing exclusive
     end offsets with seg_end[-1] == n, and the elements of segment s step at
@@ -299,6 +324,7 @@ def adamw_step_grouped(p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd,
     wd_e = torch.repeat_interleave(seg_wd.to(f32), lens)
     _adamw_update(p, grad, m, v, master, lr_e, beta1, beta2, eps, wd_e, step,
                   grad_scale)
+    _ema_update(ema, ema_decay, master)
 
 
 def grad_clip_state(grad: torch.Tensor, grad_scale: float,
@@ -322,25 +348,27 @@ def grad_clip_state(grad: torch.Tensor, grad_scale: float,
 
 
 def adamw_step_clipped(p, grad, m, v, master, lr, beta1, beta2, eps, wd,
-                       step, clip_state) -> None:
+                       step, clip_state, *, ema=None, ema_decay=None) -> None:
     """adamw_step at the clipped grad scale; a non-finite gradient
-    (clip_state[2] == 0) leaves every buffer untouched."""
+    (clip_state[2] == 0) leaves every buffer untouched, ema included."""
     if float(clip_state[2]) == 0.0:
         return
     adamw_step(p, grad, m, v, master, lr, beta1, beta2, eps, wd, step,
-               grad_scale=float(clip_state[1]))
+               grad_scale=float(clip_state[1]), ema=ema, ema_decay=ema_decay)
 
 
 def adamw_step_grouped_clipped(p, grad, m, v, master, seg_end, seg_lr_mult,
                                seg_wd, lr, beta1, beta2, eps, step,
-                               clip_state) -> None:
+                               clip_state, *, ema=None,
+                               ema_decay=None) -> None:
     """adamw_step_grouped at the clipped grad scale; a non-finite gradient
-    (clip_state[2] == 0) leaves every buffer untouched."""
+    (clip_state[2] == 0) leaves every buffer untouched, ema included."""
     if float(clip_state[2]) == 0.0:
         return
     adamw_step_grouped(p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd,
                        lr, beta1, beta2, eps, step,
-                       grad_scale=float(clip_state[1]))
+                       grad_scale=float(clip_state[1]), ema=ema,
+                       ema_decay=ema_decay)
 
 
 def dead_q_tiles(dout: torch.Tensor, n_heads: Optional[int] = None

@@ -38,8 +38,11 @@ class ClassifierService:
     def __init__(self, ckpt_dir: Optional[str] = None,
                  model: str = "mltc-base", seq: int = 256,
                  threshold: float = 0.5, device: Optional[str] = None,
-                 repo_prefix: bool = False, pack: bool = False):
+                 repo_prefix: bool = False, pack: bool = False,
+                 use_ema: bool = False):
         # pack: run one request's texts as a packed batch (data.packing)
+        # use_ema: serve the weight average the checkpoint carries (a run
+        # with ema_decay > 0); ValueError if it carries none
         self.pack = pack
         self.seq = seq
         self.threshold = threshold
@@ -61,6 +64,10 @@ class ClassifierService:
             self.trainer = Trainer(tcfg, device=self.device, model_cfg=cfg)
             if not self.trainer.load_or_init():
                 raise FileNotFoundError(f"no checkpoint in {ckpt_dir}")
+            if use_ema:
+                from tosem2021_amd.classify.neural import load_ema_weights
+                load_ema_weights(self.trainer,
+                                 Trainer.latest_checkpoint(ckpt_dir))
             self.trainer.model.eval()
             self.tok = CodeTokenizer(cfg.vocab_size)
 

@@ -13,6 +13,7 @@ atomic save, load-or-init, resume from step.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from dataclasses import dataclass
@@ -24,6 +25,7 @@ import torch.distributed as dist
 from tosem2021_amd import ops
 from tosem2021_amd.data.packing import PackedBatch
 from tosem2021_amd.models import MLTCConfig, build_model
+from tosem2021_amd.ops.reference import ema_decay_at
 from tosem2021_amd.parallel.ddp import BucketedAllReduce
 from tosem2021_amd.utils.metrics import get_metrics
 from tosem2021_amd.utils.trace import trace
@@ -58,6 +60,8 @@ class FlatParams:
         self.master = self.flat.detach().clone().float()
         self.m = torch.zeros(padded, dtype=torch.float32, device=device)
         self.v = torch.zeros(padded, dtype=torch.float32, device=device)
+        # f32 weight average, allocated by Trainer when cfg.ema_decay > 0
+        self.ema: Optional[torch.Tensor] = None
 
     def zero_grad(self):
         self.grad_flat.zero_()
@@ -125,8 +129,15 @@ class TrainConfig:
     # both at their defaults the step is the ungrouped kernel
     no_decay_1d: bool = False    # no weight decay on 1-D parameters
     layer_decay: float = 1.0     # layer-wise LR decay factor, in (0, 1]
+    # exponential moving average of the f32 master weights, kept by the fused
+    # AdamW kernel (+4 B per parameter); in [0, 1), 0 = off.  The decay of
+    # applied update t is ops.reference.ema_decay_at(ema_decay, t).
+    ema_decay: float = 0.0
 
     def __post_init__(self):
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError(
+                f"ema_decay must be in [0, 1), got {self.ema_decay}")
         if not 0.0 < self.layer_decay <= 1.0:
             raise ValueError(
                 f"layer_decay must be in (0, 1], got {self.layer_decay}")
@@ -168,6 +179,35 @@ class Trainer:
                                    no_decay_1d=cfg.no_decay_1d,
                                    layer_decay=cfg.layer_decay),
                 self.flat.padded, device=self.device)
+        if cfg.ema_decay > 0:
+            self.reset_ema()
+
+    # ---- weight average -----------------------------------------------------
+    def reset_ema(self):
+        """(Re-)seed the weight average from the current master weights, e.g.
+        after a warm start copied other weights into the model."""
+        if not self.cfg.ema_decay > 0:
+            raise RuntimeError("reset_ema() needs TrainConfig.ema_decay > 0")
+        f = self.flat
+        if f.ema is None:
+            f.ema = f.master.detach().clone()
+        else:
+            f.ema.copy_(f.master)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model's flat parameters hold the weight
+        average cast to the parameter dtype; on exit the previous flat buffer
+        comes back bit for bit.  Touches neither master nor model.training."""
+        f = self.flat
+        if f.ema is None:
+            raise RuntimeError("ema_weights() needs TrainConfig.ema_decay > 0")
+        saved = f.flat.detach().clone()
+        f.flat.copy_(f.ema)
+        try:
+            yield self.model
+        finally:
+            f.flat.copy_(saved)
 
     # ---- schedule -----------------------------------------------------------
     def _lr(self) -> float:
@@ -198,10 +238,18 @@ class Trainer:
         through the grouped entry points: lr is still the scheduled base
         rate, and the per-segment multiplier and weight decay come from the
         table built at construction.  The norm and the clip are global
-        either way."""
+        either way.
+
+        With cfg.ema_decay > 0 whichever entry point is picked also updates
+        the weight average.  opt_step is exact here, since _finish_step() has
+        synced the previous step, so a skipped step advances neither the
+        average (the kernel leaves it alone) nor its warm-up count."""
         f, c = self.flat, self.cfg
         hp = dict(lr=lr, beta1=c.beta1, beta2=c.beta2, eps=c.eps,
                   step=self.opt_step + 1)
+        if f.ema is not None:
+            hp.update(ema=f.ema,
+                      ema_decay=ema_decay_at(c.ema_decay, self.opt_step + 1))
         bufs = (f.flat, f.grad_flat, f.m, f.v, f.master)
         if c.max_grad_norm > 0:
             self._clip_state = ops.grad_clip_state(
@@ -305,6 +353,12 @@ class Trainer:
 
     # ---- checkpoint / resume -------------------------------------------------
     def state_dict(self) -> dict:
+        sd = self._state_dict()
+        if self.flat.ema is not None:
+            sd["ema"] = self.flat.ema
+        return sd
+
+    def _state_dict(self) -> dict:
         return {
             "step": self.step_num,
             "opt_step": self.opt_step,
@@ -350,6 +404,9 @@ class Trainer:
         self.flat.master.copy_(sd["master"])
         self.flat.m.copy_(sd["m"])
         self.flat.v.copy_(sd["v"])
+        if self.flat.ema is not None:
+            # a checkpoint from a run without the average starts it here
+            self.flat.ema.copy_(sd["ema"] if "ema" in sd else sd["master"])
         self.step_num = sd["step"]
         # checkpoints from before step skipping applied every step
         self.opt_step = sd.get("opt_step", sd["step"])
