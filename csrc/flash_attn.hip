@@ -45,19 +45,24 @@ typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
 // stride 128 B, XOR-swizzled = 4096 B.  Per kernel:
 //  fwd:          K tile | V tile | alpha [4 waves][64] f32 (1024 B; its
 //                first words double as the tail-skip / segment-range scratch
-//                before the loop)
+//                before the loop) | side [32]
 //  bwd_fused:    Q tile | dO tile | lse [32] f32 | ddot [32] f32
 //                (segmented: + the staged tile's q segment ids [32] i32)
 //  dq:           K tile
-//  dq_recompute: K tile | V tile | 16 B tail-skip scratch
+//  dq_recompute: K tile | V tile | side [32] | 16 B tail-skip scratch
+// side is the staged kv tile's per-key side data, one 4-byte word per key:
+// the mask bias (f32) or, segmented, the kv segment id (i32).  A slot of its
+// own: the scratch words are still being read when the first tile is staged.
 #define TILE_LDS_BYTES (FA_KVB * 128)
-#define FWD_LDS_BYTES (2 * TILE_LDS_BYTES + FA_WAVES * 64 * sizeof(float))
+#define SIDE_LDS_BYTES (FA_KVB * 4)
+#define FWD_LDS_BYTES                                                         \
+  (2 * TILE_LDS_BYTES + FA_WAVES * 64 * sizeof(float) + SIDE_LDS_BYTES)
 #define BWD_LDS_BYTES (2 * TILE_LDS_BYTES + 64 * sizeof(float))
 #define BWD_SEG_LDS_BYTES (BWD_LDS_BYTES + 32 * sizeof(int))
 #define DQ_LDS_BYTES TILE_LDS_BYTES
-#define DQR_LDS_BYTES (2 * TILE_LDS_BYTES + 16)
+#define DQR_LDS_BYTES (2 * TILE_LDS_BYTES + SIDE_LDS_BYTES + 16)
 // Waves per SIMD flash_dq_recompute is bounded to.  Without dropout it fits
-// two with nothing to spare (254 VGPRs); with the mask's temporaries it
+// two with nothing to spare (256 VGPRs); with the mask's temporaries it
 // spilled 56-112 B per lane under that bound, so the DROP instantiations are
 // bounded to one: lower occupancy, no scratch.
 #define FA_DQR_WAVES(drop) ((drop) ? 1 : 2)
@@ -114,6 +119,29 @@ struct FaStager {
     *(short8_t*)((char*)lds + row * 128 + kswz(row, byte)) = v;
   }
 };
+
+// Per-tile side data travels with its tile.  A kv tile's 32 mask biases or
+// segment ids (a q tile's lse, ddot and segment ids in flash_bwd_fused) are
+// loaded by threads 0..31 in the same slot as the tile's prefetch, sit in a
+// register through the iteration and go to LDS next to st.store, between the
+// loop-top barriers.  The loop body then reads them with ds_read, which
+// counts on lgkmcnt: vmcnt retires in issue order, so a global load issued
+// after the prefetch and used inside the body would drain the prefetch at
+// its first use.  fa_side_rows fills the 16 register-row values of a lane
+// half from the staged words: c_row(r, half) is four runs of four
+// consecutive rows, each starting at a multiple of four, so it is four
+// 16-byte reads.
+template <typename T>
+__device__ __forceinline__ void fa_side_rows(const T* side, int half,
+                                             T (&out)[16]) {
+  typedef __attribute__((ext_vector_type(4))) T vec4;
+#pragma unroll
+  for (int gq = 0; gq < 4; ++gq) {
+    const vec4 w = *(const vec4*)(side + 8 * gq + 4 * half);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[4 * gq + j] = w[j];
+  }
+}
 
 // Row fragment c (k = 16c .. 16c+15) of a staged tile: lane reads 8 bf16 of
 // tile row `col` — the A operand of the S/dP MFMAs.
@@ -537,6 +565,8 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
   short* k_lds = (short*)smem;
   short* v_lds = (short*)(smem + TILE_LDS_BYTES);
   float* alpha_lds = (float*)(smem + 2 * TILE_LDS_BYTES);
+  float* mb_lds = alpha_lds + FA_WAVES * 64;   // side [32]: bias or seg id
+  int* sk_lds = (int*)mb_lds;
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
@@ -603,27 +633,45 @@ flash_fwd_kernel(const short* __restrict__ q, const short* __restrict__ k,
   const FaStager st(tid);
   short8_t kv8 = st.load(k + qkv_off, kt_begin * FA_KVB, g.qkv_rs);
   short8_t vv8 = st.load(v + qkv_off, kt_begin * FA_KVB, g.qkv_rs);
+  // the tile's side word (fa_side_rows), threads 0..31
+  const bool side_ld = (SEG || mrow) && tid < FA_KVB;
+  float mb_n = 0.f;
+  int sk_n = 0;
+  if (side_ld) {
+    if constexpr (SEG) sk_n = srow[kt_begin * FA_KVB + tid];
+    else mb_n = mrow[kt_begin * FA_KVB + tid];
+  }
   for (int kt = kt_begin; kt < n_kv_eff; ++kt) {
     const int kv0 = kt * FA_KVB;
     __syncthreads();
     st.store(k_lds, kv8);
     st.store(v_lds, vv8);
+    if (side_ld) {
+      if constexpr (SEG) sk_lds[tid] = sk_n;
+      else mb_lds[tid] = mb_n;
+    }
     __syncthreads();
     if (kt + 1 < n_kv_eff) {
       kv8 = st.load(k + qkv_off, kv0 + FA_KVB, g.qkv_rs);
       vv8 = st.load(v + qkv_off, kv0 + FA_KVB, g.qkv_rs);
+      if (side_ld) {
+        if constexpr (SEG) sk_n = srow[kv0 + FA_KVB + tid];
+        else mb_n = mrow[kv0 + FA_KVB + tid];
+      }
     }
 
-    // mask-bias loads HOISTED above the QK chain: issued per register
-    // inside the softmax loop they sit exposed on the serial path between
-    // the mfma results and the exp chain.  The kv segment ids take the
-    // bias's place, per register, hoisted the same way.
+    // the staged tile's mask biases by register row, read above the QK
+    // chain so that the reads are not on the serial path between the mfma
+    // results and the exp chain.  The kv segment ids take the bias's place.
     float mb_r[16];
     int sk_r[16];
+    if constexpr (SEG) {
+      fa_side_rows(sk_lds, half, sk_r);
+    } else if (mrow) {
+      fa_side_rows(mb_lds, half, mb_r);
+    } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      if constexpr (SEG) sk_r[r] = srow[kv0 + c_row(r, half)];
-      else mb_r[r] = mrow ? mrow[kv0 + c_row(r, half)] : 0.f;
+      for (int r = 0; r < 16; ++r) mb_r[r] = 0.f;
     }
     if constexpr (SEG) {
       if (!fa_seg_tile_live(sk_r, sqA, sqB)) continue;
@@ -1004,25 +1052,41 @@ flash_bwd_fused_kernel(const short* __restrict__ q, const short* __restrict__ k,
   const FaStager st(tid);
   int qt = live.next(qt_begin, n_q), qt_next;
   short8_t qv8, dv8;
+  // the q tile's side words (fa_side_rows): lse, ddot and, segmented, the q
+  // segment id of row tid, threads 0..31; they follow the live-tile scan
+  // with the tile they belong to
+  const bool side_ld = tid < 32;
+  float lse_n = 0.f, dd_n = 0.f;
+  int sq_n = 0;
   if (qt < n_q) {
     qv8 = st.load(q + qkv_off, qt * 32, g.qkv_rs);
     dv8 = st.load(dout + o_off, qt * 32, g.o_rs);
+    if (side_ld) {
+      lse_n = lse[(long)bh * L + qt * 32 + tid];
+      dd_n = ddot[(long)bh * L + qt * 32 + tid];
+      if constexpr (SEG) sq_n = srow[qt * 32 + tid];
+    }
   }
   for (; qt < n_q; qt = qt_next) {
     const int q0 = qt * 32;
     __syncthreads();
     st.store(q_lds, qv8);
     st.store(do_lds, dv8);
-    if (tid < 32) {
-      lse_lds[tid] = lse[(long)bh * L + q0 + tid];
-      dd_lds[tid] = ddot[(long)bh * L + q0 + tid];
-      if constexpr (SEG) seg_lds[tid] = srow[q0 + tid];
+    if (side_ld) {
+      lse_lds[tid] = lse_n;
+      dd_lds[tid] = dd_n;
+      if constexpr (SEG) seg_lds[tid] = sq_n;
     }
     __syncthreads();
     qt_next = live.next(qt + 1, n_q);
     if (qt_next < n_q) {
       qv8 = st.load(q + qkv_off, qt_next * 32, g.qkv_rs);
       dv8 = st.load(dout + o_off, qt_next * 32, g.o_rs);
+      if (side_ld) {
+        lse_n = lse[(long)bh * L + qt_next * 32 + tid];
+        dd_n = ddot[(long)bh * L + qt_next * 32 + tid];
+        if constexpr (SEG) sq_n = srow[qt_next * 32 + tid];
+      }
     }
 
     if (wave_skip) continue;
@@ -1354,7 +1418,9 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   extern __shared__ __attribute__((aligned(16))) char smem[];
   short* k_lds = (short*)smem;
   short* v_lds = (short*)(smem + TILE_LDS_BYTES);
-  int* skip_scratch = (int*)(smem + 2 * TILE_LDS_BYTES);
+  float* mb_lds = (float*)(smem + 2 * TILE_LDS_BYTES);   // side [32]
+  int* sk_lds = (int*)mb_lds;
+  int* skip_scratch = (int*)(smem + 2 * TILE_LDS_BYTES + SIDE_LDS_BYTES);
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
@@ -1463,24 +1529,43 @@ flash_dq_recompute_kernel(const short* __restrict__ q,
   const FaStager st(tid);
   short8_t kv8 = st.load(k + qkv_off, kt_begin * FA_KVB, g.qkv_rs);
   short8_t vv8 = st.load(v + qkv_off, kt_begin * FA_KVB, g.qkv_rs);
+  // the tile's side word (fa_side_rows), threads 0..31
+  const bool side_ld = (SEG || mrow) && tid < FA_KVB;
+  float mb_n = 0.f;
+  int sk_n = 0;
+  if (side_ld) {
+    if constexpr (SEG) sk_n = srow[kt_begin * FA_KVB + tid];
+    else mb_n = mrow[kt_begin * FA_KVB + tid];
+  }
   for (int kt = kt_begin; kt < n_kv_eff; ++kt) {
     const int kv0 = kt * FA_KVB;
     __syncthreads();
     st.store(k_lds, kv8);
     st.store(v_lds, vv8);
+    if (side_ld) {
+      if constexpr (SEG) sk_lds[tid] = sk_n;
+      else mb_lds[tid] = mb_n;
+    }
     __syncthreads();
     if (kt + 1 < n_kv_eff) {
       kv8 = st.load(k + qkv_off, kv0 + FA_KVB, g.qkv_rs);
       vv8 = st.load(v + qkv_off, kv0 + FA_KVB, g.qkv_rs);
+      if (side_ld) {
+        if constexpr (SEG) sk_n = srow[kv0 + FA_KVB + tid];
+        else mb_n = mrow[kv0 + FA_KVB + tid];
+      }
     }
     if (wave_dead) continue;
 
     float mb_r[16];
     int sk_r[16];
+    if constexpr (SEG) {
+      fa_side_rows(sk_lds, half, sk_r);
+    } else if (mrow) {
+      fa_side_rows(mb_lds, half, mb_r);
+    } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      if constexpr (SEG) sk_r[r] = srow[kv0 + c_row(r, half)];
-      else mb_r[r] = mrow ? mrow[kv0 + c_row(r, half)] : 0.f;
+      for (int r = 0; r < 16; ++r) mb_r[r] = 0.f;
     }
     if constexpr (SEG) {
       if (!fa_seg_tile_live(sk_r, sqA, sqB)) continue;

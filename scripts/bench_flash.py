@@ -1,12 +1,17 @@
 """Standalone flash-attention kernel microbench (for rocprofv3 PMC runs).
 
-    python scripts/bench_flash.py [iters] [--zero-do-tail]
+    python scripts/bench_flash.py [iters] [--zero-do-tail] [--bench-mask]
 
 --zero-do-tail zeroes dO where the mask is padding (rows 400..511), as the
 model's backward does, so the dead-query-tile skip has something to skip; the
 three backward kernels (fa_dot, flash_bwd_fused, flash_dq_recompute) are
 reported with and without the flags either way.  With random dO nothing is
-skippable and the pair of figures is the cost of the flag test."""
+skippable and the pair of figures is the cost of the flag test.
+
+--bench-mask takes the padding mask of bench.py's batch instead of the fixed
+400 live keys: synthetic_batch's per-row lengths, uniform in [256, 512], so
+the workgroups of one launch see tails of different lengths as they do in
+the model step."""
 import sys, os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import time
 
@@ -19,14 +24,22 @@ def main():
     B, H, L, dh = 128, 16, 512, 64
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     zero_tail = "--zero-do-tail" in sys.argv[1:]
+    bench_mask = "--bench-mask" in sys.argv[1:]
     iters = int(args[0]) if args else 30
     torch.manual_seed(0)
     q = torch.randn(B, H, L, dh, device="cuda", dtype=torch.bfloat16)
     k = torch.randn_like(q)
     v = torch.randn_like(q)
     mask = torch.zeros(B, L, device="cuda")
-    mask[:, 400:] = -1e9
+    if bench_mask:
+        from tosem2021_amd.data.synthetic import synthetic_batch
+        from tosem2021_amd.models.classifier import CONFIGS
+        _, live, _ = synthetic_batch(CONFIGS["mltc-base"], B, L, device="cuda")
+        mask[~live] = -1e9
+    else:
+        mask[:, 400:] = -1e9
     mask = mask.contiguous()
+    pad = (mask < 0).view(B, 1, L, 1)       # padded rows, over heads and dh
     scale = 0.125
     ext = ops.hip_ops()
     for _ in range(5):
@@ -42,7 +55,7 @@ def main():
     # bwd stage (round-2 default: dk/dv only, no dS materialization)
     do = torch.randn_like(q)
     if zero_tail:
-        do[:, :, 400:] = 0
+        do.masked_fill_(pad, 0)
     ddot = ext.fa_dot(do, o)
 
     # the three backward kernels, without and with the dead-tile flags
@@ -129,7 +142,7 @@ def main():
     qkv = torch.randn(B, L, 3 * H * dh, device="cuda", dtype=torch.bfloat16)
     dop = torch.randn(B, L, H * dh, device="cuda", dtype=torch.bfloat16)
     if zero_tail:
-        dop[:, 400:] = 0
+        dop.masked_fill_(pad.view(B, L, 1), 0)
     o, lse = ext.flash_fwd_packed(qkv, H, mask, scale)
     dt0 = timed(lambda: ext.flash_bwd_packed(qkv, o, dop, mask, lse, H,
                                              scale))
