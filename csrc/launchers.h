@@ -48,6 +48,15 @@ hipError_t ln_drop_bwd_launch(const void* dy, const void* x,
                               unsigned site, unsigned thr,
                               hipStream_t stream);
 int ln_drop_bwd_max_d(void);
+// MX output (inference; mx_quant.hip below for the format): as ln_fwd_launch
+// without mean and rstd, and instead of y the MXFP8 form of the bf16 values y
+// would hold: q [N, D] e4m3 bytes, scales [N, D / 32] e8m0 bytes.  D % 32 == 0,
+// D <= ln_mx_fwd_max_d() (hipErrorInvalidValue otherwise).
+hipError_t ln_mx_fwd_launch(const void* x, const void* res, const void* gamma,
+                            const void* beta, void* q, void* scales,
+                            void* s_out, int N, int D, float eps,
+                            hipStream_t stream);
+int ln_mx_fwd_max_d(void);
 
 // ---- colsum.hip -------------------------------------------------------------
 // ws [R, D] f32 -> out [D] (f32, or bf16 with out_bf16).  scratch is
@@ -72,6 +81,17 @@ hipError_t bias_gelu_bwd_launch(const void* dy, const void* x, const void* b,
                                 void* dx, void* ws_dbias, long n_elem, int D,
                                 hipStream_t stream);
 int bias_gelu_bwd_ws_rows(long n_elem, int D);
+
+// ---- mx_quant.hip -----------------------------------------------------------
+// OCP MXFP8 along K: x, h [R, K] bf16, K % 32 == 0 -> q [R, K] uint8 (e4m3fn
+// bytes) and s [R, K / 32] uint8 (e8m0: one power-of-two scale per 32
+// consecutive elements), bit for bit ops.reference.mx_quantize of x, or of
+// bf16(gelu_tanh(h + b)) with b [K] bf16, the value bias_gelu_fwd_launch
+// stores.
+hipError_t mx_quant_rows_launch(const void* x, void* q, void* s, long R, int K,
+                                hipStream_t stream);
+hipError_t mx_bias_gelu_launch(const void* h, const void* b, void* q, void* s,
+                               long R, int K, hipStream_t stream);
 
 // ---- softmax.hip ------------------------------------------------------------
 // s, p, dp, ds [n_rows, Lk] bf16; mask (nullptr = none) [B, Lk] f32 with

@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "mx.h"
 #include "philox.h"
 #include <cstdlib>
 #include <cstring>
@@ -63,7 +64,45 @@ __device__ __forceinline__ short drop_grad(float v, bool keep, float scale) {
   return keep ? f32_to_bf16(v * scale) : (short)0;
 }
 
-template <bool DROP>
+// MX output mode of the two forward kernels (inference; mx.h,
+// docs/KERNELS.md "MXFP8 operands"): the normalised value is rounded to bf16
+// in registers exactly as the bf16 mode stores it, and that packet is
+// quantised instead of stored.  The bodies are shared, so the arithmetic
+// order is.
+//
+// READ THIS before touching the MX instantiations: they keep the bf16
+// kernels' parameter list, so that the bf16 instantiations compile to what
+// they were, and two of its pointers carry other data under other types:
+//
+//   parameter           bf16 mode               MX mode
+//   short* y            y [N, D] bf16           q [N, D] e4m3 BYTES
+//   float* mean_out     mean [N] f32            scales [N, D / 32] e8m0 BYTES
+//   float* rstd_out     rstd [N] f32            nullptr, never touched
+//
+// LnMxOut names the two under their real types, and every MX access goes
+// through it; `y`, `mean_out` and `rstd_out` themselves are only
+// dereferenced under !MX.  D % 32 == 0, so in the general path a lane quad
+// enters or leaves the packet loop as a whole.
+struct LnMxOut {
+  unsigned char* q;       // [N, D] e4m3fn bytes
+  unsigned char* scales;  // [N, D / 32] e8m0 bytes
+};
+__device__ __forceinline__ LnMxOut ln_mx_out(short* y, float* mean_out) {
+  return LnMxOut{(unsigned char*)y, (unsigned char*)mean_out};
+}
+
+// One packet of the output: to dst (bf16 mode), or quantised to element
+// offset elem of mx (MX mode).
+template <bool MX>
+__device__ __forceinline__ void ln_store_out(short8_t o, short* dst, long elem,
+                                             LnMxOut mx) {
+  if (MX)
+    mx_store_packet(o, elem, mx.q, mx.scales);
+  else
+    *(short8_t*)dst = o;
+}
+
+template <bool DROP, bool MX>
 __global__ void __launch_bounds__(BLOCK)
 ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
               const short* __restrict__ gamma,
@@ -127,7 +166,7 @@ ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
       }
       var = wave_sum(var) / (float)D;
       float rstd = rsqrtf(var + eps);
-      if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
+      if (!MX && lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
 #pragma unroll
       for (int p = 0; p < MAX_PKT; ++p) {
         if (p >= pkts) break;
@@ -140,7 +179,8 @@ ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
           float xhat = (vals[p * 8 + j] - mean) * rstd;
           o[j] = f32_to_bf16(xhat * bf16_to_f32(g8[j]) + bf16_to_f32(b8[j]));
         }
-        *(short8_t*)(yr + base) = o;
+        ln_store_out<MX>(o, yr + base, (long)row * D + base,
+                         ln_mx_out(y, mean_out));
       }
     } else {
       // general path: two passes over the row, 8-wide loads, any D % 8 == 0
@@ -176,7 +216,7 @@ ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
       }
       var = wave_sum(var) / (float)D;
       float rstd = rsqrtf(var + eps);
-      if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
+      if (!MX && lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
       for (int i = lane * 8; i < D; i += WAVE * 8) {
         short8_t v = *(const short8_t*)((rr ? sr : xr) + i);
         short8_t g8 = *(const short8_t*)(gamma + i);
@@ -187,7 +227,8 @@ ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
           float xhat = (bf16_to_f32(v[j]) - mean) * rstd;
           o[j] = f32_to_bf16(xhat * bf16_to_f32(g8[j]) + bf16_to_f32(b8[j]));
         }
-        *(short8_t*)(yr + i) = o;
+        ln_store_out<MX>(o, yr + i, (long)row * D + i,
+                         ln_mx_out(y, mean_out));
       }
     }
   }
@@ -197,7 +238,7 @@ ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
 // MAX_PKT-sized register waste), gamma/beta hoisted out of the row loop,
 // and the NEXT row's packets prefetched before the wave-reduction chains so
 // the loads overlap the two log2(64) shuffle reductions.  One wave per row.
-template <int PKTS, bool HASRES, bool DROP>
+template <int PKTS, bool HASRES, bool DROP, bool MX>
 __global__ void __launch_bounds__(BLOCK)
 ln_fwd_t(const short* __restrict__ x, const short* __restrict__ res,
          const short* __restrict__ gamma, const short* __restrict__ beta,
@@ -274,7 +315,7 @@ ln_fwd_t(const short* __restrict__ x, const short* __restrict__ res,
     }
     var = wave_sum(var) / (float)D;
     float rstd = rsqrtf(var + eps);
-    if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
+    if (!MX && lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
 #pragma unroll
     for (int p = 0; p < PKTS; ++p) {
       short8_t o;
@@ -283,7 +324,8 @@ ln_fwd_t(const short* __restrict__ x, const short* __restrict__ res,
         int k = p * 8 + j;
         o[j] = f32_to_bf16((vals[k] - mean) * rstd * gv[k] + bv[k]);
       }
-      *(short8_t*)(y + (long)row * D + (p * WAVE + lane) * 8) = o;
+      const long elem = (long)row * D + (p * WAVE + lane) * 8;
+      ln_store_out<MX>(o, y + elem, elem, ln_mx_out(y, mean_out));
     }
     if (next >= N) break;
     row = next;
@@ -777,12 +819,15 @@ static int ln_bwd_grid(int N, int D) {
 // One dispatch per direction, shared by the plain and the dropout launchers:
 // DROP only selects the instantiation, so both take the same kernel variant
 // and the same grid at every width.
-template <bool DROP>
+// MX (never with DROP) selects the MX-output kernel of the same variant:
+// y = q, mean = the scale bytes, rstd = nullptr (the table at LnMxOut above).
+template <bool DROP, bool MX = false>
 static hipError_t ln_fwd_dispatch(const void* x, const void* res,
                                   const void* gamma, const void* beta, void* y,
                                   void* s_out, void* mean, void* rstd, int N,
                                   int D, float eps, LnDrop dr,
                                   hipStream_t stream) {
+  static_assert(!(DROP && MX), "no dropout in the MX output mode");
   const int grid = ln_row_blocks(N, LN_FWD_MAX_GRID);
 #define LNF_ARGS                                                              \
   (const short*)x, (const short*)res, (const short*)gamma,                    \
@@ -790,10 +835,16 @@ static hipError_t ln_fwd_dispatch(const void* x, const void* res,
       (float*)rstd, N, D, eps, dr
 #define LNF_T(P)                                                              \
   do {                                                                        \
-    if (res) {                                                                \
-      ln_fwd_t<P, true, DROP><<<grid, BLOCK, 0, stream>>>(LNF_ARGS);          \
+    if constexpr (MX) {                                                       \
+      if (res) {                                                              \
+        ln_fwd_t<P, true, false, true><<<grid, BLOCK, 0, stream>>>(LNF_ARGS);  \
+      } else {                                                                \
+        ln_fwd_t<P, false, false, true><<<grid, BLOCK, 0, stream>>>(LNF_ARGS); \
+      }                                                                       \
+    } else if (res) {                                                         \
+      ln_fwd_t<P, true, DROP, false><<<grid, BLOCK, 0, stream>>>(LNF_ARGS);   \
     } else if constexpr (!DROP) {                                             \
-      ln_fwd_t<P, false, false><<<grid, BLOCK, 0, stream>>>(LNF_ARGS);        \
+      ln_fwd_t<P, false, false, false><<<grid, BLOCK, 0, stream>>>(LNF_ARGS); \
     }                                                                         \
   } while (0)
   if (D == 512) LNF_T(1);
@@ -801,8 +852,10 @@ static hipError_t ln_fwd_dispatch(const void* x, const void* res,
   else if (D == 2048) LNF_T(4);
   // PKTS=8 (D=4096) allocates 256 VGPRs (1 wave/SIMD) — the general kernel
   // is the better trade there
+  else if constexpr (MX)
+    ln_fwd_kernel<false, true><<<grid, BLOCK, 0, stream>>>(LNF_ARGS);
   else
-    ln_fwd_kernel<DROP><<<grid, BLOCK, 0, stream>>>(LNF_ARGS);
+    ln_fwd_kernel<DROP, false><<<grid, BLOCK, 0, stream>>>(LNF_ARGS);
 #undef LNF_T
 #undef LNF_ARGS
   return hipGetLastError();
@@ -937,6 +990,18 @@ hipError_t ln_drop_fwd_launch(const void* x, const void* res,
   return ln_fwd_dispatch<true>(x, res, gamma, beta, y, s_out, mean, rstd, N,
                                D, eps, dr, stream);
 }
+
+hipError_t ln_mx_fwd_launch(const void* x, const void* res, const void* gamma,
+                            const void* beta, void* q, void* scales,
+                            void* s_out, int N, int D, float eps,
+                            hipStream_t stream) {
+  if (D <= 0 || D % 32 || D > ln_mx_fwd_max_d() || !res != !s_out)
+    return hipErrorInvalidValue;
+  return ln_fwd_dispatch<false, true>(x, res, gamma, beta, q, s_out, scales,
+                                      nullptr, N, D, eps, LnDrop{}, stream);
+}
+
+int ln_mx_fwd_max_d(void) { return 4096; }
 
 // ws is [ln_bwd_ws_rows(N, D), n_out * D] f32 with n_out = 2
 // ([dgamma | dbeta]) or 3 (+ [dres_sum]); every width supports both.

@@ -370,6 +370,82 @@ torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor b) {
   return y;
 }
 
+// ---- MXFP8 operands (csrc/mx_quant.hip, MX output of csrc/layernorm.hip) ----
+// Every producer returns {q, s}: uint8 e4m3fn bytes shaped like the bf16
+// tensor they stand for, and uint8 e8m0 bytes [..., K / 32].
+
+namespace {
+
+long mx_check_k(const torch::Tensor& x, const char* name) {
+  const long K = x.size(-1);
+  TORCH_CHECK(K > 0 && K % 32 == 0, name, " needs a last dim that is a "
+              "multiple of 32 for MXFP8, got ", K);
+  return K;
+}
+
+std::pair<torch::Tensor, torch::Tensor> mx_outputs(const torch::Tensor& x,
+                                                   long K) {
+  auto u8 = x.options().dtype(torch::kUInt8);
+  auto ssz = x.sizes().vec();
+  ssz.back() = K / 32;
+  return {torch::empty(x.sizes(), u8), torch::empty(ssz, u8)};
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> mx_quant_rows(torch::Tensor x) {
+  check_bf16(x, "x");
+  const long K = mx_check_k(x, "x");
+  auto [q, s] = mx_outputs(x, K);
+  if (x.numel() == 0) return {q, s};
+  CHECK_HIP(mx_quant_rows_launch(x.data_ptr(), q.data_ptr(), s.data_ptr(),
+                                 x.numel() / K, (int)K, cur_stream()));
+  return {q, s};
+}
+
+std::vector<torch::Tensor> mx_bias_gelu(torch::Tensor h, torch::Tensor b) {
+  check_bf16(h, "h"); check_bf16(b, "b");
+  const long K = mx_check_k(h, "h");
+  check_numel(b, "b", K, "[K]");
+  auto [q, s] = mx_outputs(h, K);
+  if (h.numel() == 0) return {q, s};
+  CHECK_HIP(mx_bias_gelu_launch(h.data_ptr(), b.data_ptr(), q.data_ptr(),
+                                s.data_ptr(), h.numel() / K, (int)K,
+                                cur_stream()));
+  return {q, s};
+}
+
+// {q, s, sum}: the MXFP8 form of layernorm_fwd's y, and its s_out (x itself
+// without a residual).  No mean or rstd: inference only.
+std::vector<torch::Tensor> mx_layernorm_fwd(
+    torch::Tensor x, c10::optional<torch::Tensor> residual,
+    torch::Tensor gamma, torch::Tensor beta, double eps) {
+  check_bf16(x, "x"); check_bf16(gamma, "gamma"); check_bf16(beta, "beta");
+  const long D = mx_check_k(x, "x");
+  TORCH_CHECK(D <= ln_mx_fwd_max_d(), "LayerNorm with MX output covers D <= ",
+              ln_mx_fwd_max_d(), ", got ", D);
+  const long N = x.numel() / D;
+  check_numel(gamma, "gamma", D, "[D]");
+  check_numel(beta, "beta", D, "[D]");
+  auto [q, s] = mx_outputs(x, D);
+  const void* res_ptr = nullptr;
+  torch::Tensor sum = x;
+  void* sum_ptr = nullptr;
+  if (residual.has_value()) {
+    check_bf16(*residual, "residual");
+    TORCH_CHECK(residual->sizes() == x.sizes(), "residual shape mismatch");
+    res_ptr = residual->data_ptr();
+    sum = torch::empty_like(x);
+    sum_ptr = sum.data_ptr();
+  }
+  if (N == 0) return {q, s, sum};
+  CHECK_HIP(ln_mx_fwd_launch(x.data_ptr(), res_ptr, gamma.data_ptr(),
+                             beta.data_ptr(), q.data_ptr(), s.data_ptr(),
+                             sum_ptr, (int)N, (int)D, (float)eps,
+                             cur_stream()));
+  return {q, s, sum};
+}
+
 // dbias is f32, or bf16 with out_bf16 (rounded by the final colsum stage).
 std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
                                          torch::Tensor b, bool out_bf16) {
@@ -1225,6 +1301,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rstd"), py::arg("ds_extra"), py::arg("out_bf16"),
         py::arg("seed"), py::arg("call"), py::arg("site"), py::arg("thr"));
   m.def("bias_gelu_fwd", &bias_gelu_fwd, "fused bias+GeLU fwd");
+  m.def("mx_quant_rows", &mx_quant_rows, "bf16 -> MXFP8 (q, s) along K");
+  m.def("mx_bias_gelu", &mx_bias_gelu,
+        "MXFP8 (q, s) of gelu_tanh(h + b), inference");
+  m.def("mx_layernorm_fwd", &mx_layernorm_fwd,
+        "(Add+)LayerNorm with MXFP8 output (q, s, sum), inference");
   m.def("lt_linear_gelu_bias", &lt_linear_gelu_bias,
         "hipBLASLt GEMM with fused GELU_BIAS epilogue (inference)");
   m.def("lt_bench_algos", &lt_bench_algos,

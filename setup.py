@@ -28,6 +28,7 @@ ext = CUDAExtension(
         "csrc/layernorm.hip",
         "csrc/colsum.hip",
         "csrc/bias_gelu.hip",
+        "csrc/mx_quant.hip",
         "csrc/softmax.hip",
         "csrc/adamw.hip",
         "csrc/grad_norm.hip",

@@ -473,13 +473,15 @@ def apply_classifier(ckpt_dir: str, taxonomy_path: str, out_csv: str,
                      batch: int = 64, threshold: float = 0.5,
                      device: Optional[str] = None,
                      repo_prefix: bool = False, pack: bool = False,
-                     use_ema: bool = False) -> str:
+                     use_ema: bool = False, mx: bool = False) -> str:
     """Label the rows of a (mined) taxonomy CSV with a trained MLTC model and
     rewrite the 41-column CSV with the predicted labels.  `pack` runs each
     chunk of `batch` texts as one packed batch; the rows come out in input
     order either way.  `use_ema` labels with the weight average that a run
     with `ema_decay` > 0 saved next to the raw weights; a checkpoint without
-    one is a ValueError."""
+    one is a ValueError.  `mx` runs the four projections of every block on
+    MXFP8 operands (MLTC.quantize_mx), quantised from the weights just
+    loaded, the average included."""
     from tosem2021_amd.extract.schema import (
         METHODS, PROPERTIES, STAGES, STRATEGIES, STRATEGY_TO_COLUMNS,
         TestCaseRow)
@@ -499,6 +501,8 @@ def apply_classifier(ckpt_dir: str, taxonomy_path: str, out_csv: str,
     if use_ema:
         load_ema_weights(trainer, Trainer.latest_checkpoint(ckpt_dir))
     trainer.model.eval()
+    if mx:
+        trainer.model.quantize_mx()
 
     texts = (df["Labels"].astype(str) + " | " +
              df["Component"].astype(str)).tolist()

@@ -129,7 +129,7 @@ def cmd_classify(args):
                            model=args.model, seq=args.seq,
                            threshold=args.threshold,
                            repo_prefix=args.repo_prefix, pack=args.pack,
-                           use_ema=args.ema)
+                           use_ema=args.ema, mx=args.mx)
     print(f"wrote {out}")
 
 
@@ -235,6 +235,10 @@ def main(argv=None):
     p.add_argument("--ema", action="store_true",
                    help="label with the weight average of a checkpoint "
                         "trained with --ema-decay")
+    p.add_argument("--mx", action="store_true",
+                   help="run the encoder's projections on MXFP8 operands "
+                        "(quantised from the loaded weights, the average "
+                        "with --ema)")
     p.set_defaults(fn=cmd_classify)
 
     p = sub.add_parser("train", help="train the MLTC classifier on a taxonomy")

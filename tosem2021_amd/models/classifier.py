@@ -186,28 +186,37 @@ class Attention(nn.Module):
         attn_drop: (p, seed, call) of this forward's dropout on the
         attention probabilities (never together with fold_bias); the mask
         is reference.attn_dropout_keep's for this block's layer."""
-        B, L, D = x.shape
         dropout = None if attn_drop is None else (*attn_drop, self.layer)
+        if ops.flash_supported(self.head_dim, x.shape[1]):
+            # (with fold_bias the flash backward also returns qkv.bias's
+            # gradient, the column sum of the dqkv it writes)
+            qkv = _linear(self.qkv, x, fold_bias)
+        else:
+            qkv = self.qkv(x)
+        out = self._attend(qkv, mask_bias, seg, fold_bias, dropout)
+        return _linear(self.proj, out, fold_bias)
+
+    def _attend(self, qkv, mask_bias, seg, fold_bias: bool = False,
+                dropout=None):
+        """[B, L, 3D] packed projection output -> [B, L, D] attention output,
+        ready for proj.  dropout: (p, seed, call, layer) or None."""
+        B, L, _ = qkv.shape
         if ops.flash_supported(self.head_dim, L):
             # MFMA flash kernels run straight on the packed [B, L, 3D]
             # projection output and write attention out (and, in backward,
             # every gradient) in the packed layouts — no repack kernels,
             # no [L, L] score tensor, O(L) attention memory
-            # (with fold_bias the flash backward also returns qkv.bias's
-            # gradient, the column sum of the dqkv it writes)
-            out = ops.flash_attention_packed(
-                _linear(self.qkv, x, fold_bias), self.n_heads, mask_bias,
-                self.scale, seg, self.qkv.bias if fold_bias else None,
-                dropout)
-            return _linear(self.proj, out, fold_bias)
-        if dropout is not None and x.is_cuda:
+            return ops.flash_attention_packed(
+                qkv, self.n_heads, mask_bias, self.scale, seg,
+                self.qkv.bias if fold_bias else None, dropout)
+        if dropout is not None and qkv.is_cuda:
             # no O(L^2) fallback: P exists only inside the flash kernels
             raise RuntimeError(
                 "attention dropout on the GPU needs the flash kernels: "
                 f"head_dim 64 and L % 32 == 0, got head_dim {self.head_dim}, "
                 f"L {L}")
         if seg is not None or dropout is not None:
-            if x.is_cuda:
+            if qkv.is_cuda:
                 # no O(L^2) fallback: packing exists to cut attention work
                 raise RuntimeError(
                     "sequence packing on the GPU needs the segment-aware "
@@ -215,7 +224,7 @@ class Attention(nn.Module):
                     f"head_dim {self.head_dim}, L {L}")
             # CPU reference for any shape: plain softmax over the
             # segment (or padding) bias, times the reference dropout mask
-            q, k, v = ops.qkv_repack(self.qkv(x), self.n_heads)
+            q, k, v = ops.qkv_repack(qkv, self.n_heads)
             s = torch.matmul(q, k.transpose(-1, -2)).float() * self.scale
             if seg is not None:
                 s = s + ops.reference.segment_bias(seg)
@@ -228,14 +237,25 @@ class Attention(nn.Module):
                 p = p * keep * ops.reference.attn_dropout_threshold(
                     dropout[0])[1]
             out = torch.matmul(p.to(v.dtype), v)
-            return _linear(self.proj, ops.out_repack(out), fold_bias)
+            return ops.out_repack(out)
         # general-shape fallback: gather kernel to bmm-ready
         # [3, B, H, L, dh] (csrc/repack.hip), bmm + fused softmax
-        q, k, v = ops.qkv_repack(self.qkv(x), self.n_heads)  # [B, H, L, dh]
+        q, k, v = ops.qkv_repack(qkv, self.n_heads)         # [B, H, L, dh]
         scores = torch.matmul(q, k.transpose(-1, -2))  # [B, H, L, L]
         p = ops.fused_softmax(scores, mask_bias, self.scale)
-        out = torch.matmul(p, v)                       # [B, H, L, dh]
-        return _linear(self.proj, ops.out_repack(out), fold_bias)
+        return ops.out_repack(torch.matmul(p, v))      # [B, L, D]
+
+    def forward_mx(self, q, s, mask_bias, seg=None):
+        """forward on the MXFP8 form (q, s) of the normalised input, with
+        the weights MLTC.quantize_mx() left on qkv and proj.  Attention
+        itself is unchanged: the qkv GEMM writes bf16, and the attention
+        output is quantised on its way into proj."""
+        dt = self.qkv.weight.dtype
+        qkv = ops.mx_linear(q, s, self.qkv.mx_q, self.qkv.mx_s, self.qkv.bias,
+                            dt)
+        out = self._attend(qkv, mask_bias, seg)
+        return ops.mx_linear(*ops.mx_quant_rows(out), self.proj.mx_q,
+                             self.proj.mx_s, self.proj.bias, dt)
 
 
 class FFN(nn.Module):
@@ -257,6 +277,16 @@ class FFN(nn.Module):
         h = _linear(self.up, x)
         h = ops.fused_bias_gelu(h, self.up_bias)
         return _linear(self.down, h, fold_bias)
+
+    def forward_mx(self, q, s):
+        """forward on the MXFP8 form (q, s) of the normalised input: the up
+        GEMM writes bf16 without bias, and one kernel adds the bias, applies
+        GeLU and quantises the down GEMM's operand."""
+        dt = self.up.weight.dtype
+        h = ops.mx_linear(q, s, self.up.mx_q, self.up.mx_s, None, dt)
+        return ops.mx_linear(*ops.mx_bias_gelu(h, self.up_bias),
+                             self.down.mx_q, self.down.mx_s, self.down.bias,
+                             dt)
 
 
 class EncoderBlock(nn.Module):
@@ -317,6 +347,24 @@ class EncoderBlock(nn.Module):
         h2 = self._drop(self.ffn(y2, fold_bias))
         return s2, h2
 
+    def forward_mx(self, x, delta, mask_bias, seg=None):
+        """forward with MXFP8 projections (MLTC.quantize_mx; eval mode, no
+        grad): LN-MX -> qkv -> attention (unchanged) -> quantise -> proj ->
+        add+LN-MX -> up -> bias+GeLU+quantise -> down.  The LayerNorm
+        kernels hand the GEMMs their quantised operand directly; the
+        (stream, delta) pair travels as in forward."""
+        if delta is None:
+            q, s = ops.mx_layernorm(x, self.ln1.weight, self.ln1.bias,
+                                    self.ln1.eps)
+            s1 = x
+        else:
+            q, s, s1 = ops.mx_add_layernorm(x, delta, self.ln1.weight,
+                                            self.ln1.bias, self.ln1.eps)
+        h = self.attn.forward_mx(q, s, mask_bias, seg)
+        q, s, s2 = ops.mx_add_layernorm(s1, h, self.ln2.weight, self.ln2.bias,
+                                        self.ln2.eps)
+        return s2, self.ffn.forward_mx(q, s)
+
     def _forward_fused_dropout(self, x, delta, mask_bias, seg, drop, index,
                                attn_drop=None):
         if delta is None:
@@ -351,6 +399,8 @@ class MLTC(nn.Module):
         # ranks draw different masks
         self.dropout_call = 0
         self.dropout_rank = 0
+        # quantize_mx(): the weights' version stamps at quantisation time
+        self._mx_versions = None
         self.tok_emb = nn.Embedding(cfg.vocab_size, cfg.d_model)
         self.pos_emb = nn.Embedding(cfg.max_seq, cfg.d_model)
         self.blocks = nn.ModuleList(EncoderBlock(cfg, i)
@@ -398,7 +448,83 @@ class MLTC(nn.Module):
         return ((cfg.dropout, seed, call) if fused else None,
                 (cfg.attn_dropout, seed, call) if attn else None)
 
+    def _mx_linears(self):
+        """The projections quantize_mx covers, block by block."""
+        for blk in self.blocks:
+            yield from (blk.attn.qkv, blk.attn.proj, blk.ffn.up, blk.ffn.down)
+
+    @torch.no_grad()
+    def quantize_mx(self) -> "MLTC":
+        """Serve with MXFP8 projections: quantise attn.qkv, attn.proj, ffn.up
+        and ffn.down of every block (ops.mx_quant_rows along K) into
+        non-persistent buffers mx_q, mx_s on those modules.  Parameters, the
+        state dict and checkpoints do not change; embeddings, attention, the
+        pool and the heads stay as they are.  From here until clear_mx() an
+        eval-mode forward under no_grad runs EncoderBlock.forward_mx; one in
+        training mode or with grad enabled raises, and so does one after a
+        weight has been written (an EMA swap, a checkpoint load, an
+        optimizer step; _mx_weight_versions says how that is seen under a
+        Trainer): call quantize_mx() again.  Load the weights first, then
+        quantise."""
+        self.clear_mx()
+        for lin in self._mx_linears():
+            q, s = ops.mx_quant_rows(lin.weight.detach())
+            lin.register_buffer("mx_q", q, persistent=False)
+            lin.register_buffer("mx_s", s, persistent=False)
+        self._mx_versions = self._mx_weight_versions()
+        return self
+
+    def _mx_weight_versions(self):
+        """What a write to a quantised projection's weight moves: the
+        parameter's own version counter and, for a model whose parameters
+        are views into a trainer's flat buffer (train.FlatParams marks them
+        with `_flat_owner`), that buffer's.  Rebinding `p.data` to a view
+        leaves the parameter its own counter, so `flat.copy_(...)`, which is
+        how an EMA swap and a checkpoint load write, shows only on the
+        owner; the fused AdamW step writes through raw pointers and the
+        Trainer bumps the owner's counter itself."""
+        out = []
+        for lin in self._mx_linears():
+            owner = getattr(lin.weight, "_flat_owner", None)
+            out.append((lin.weight._version, lin.weight.data_ptr(),
+                        None if owner is None else owner._version))
+        return out
+
+    def clear_mx(self) -> "MLTC":
+        """Drop quantize_mx()'s buffers: forwards run the bf16 path again."""
+        for lin in self._mx_linears():
+            for name in ("mx_q", "mx_s"):
+                if hasattr(lin, name):
+                    delattr(lin, name)
+        self._mx_versions = None
+        return self
+
+    @property
+    def mx_active(self) -> bool:
+        return self._mx_versions is not None
+
+    def _run_blocks_mx(self, x, mask_bias, seg):
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError(
+                "the model is quantised for MXFP8 serving (quantize_mx): "
+                "run it in eval mode under torch.no_grad(), or call "
+                "clear_mx() first")
+        if self._mx_versions != self._mx_weight_versions():
+            raise RuntimeError(
+                "weights changed since quantize_mx(): the quantised copies "
+                "are stale; call quantize_mx() again")
+        delta = None
+        for blk in self.blocks:
+            x, delta = blk.forward_mx(x, delta, mask_bias, seg)
+        if delta is None:
+            return self.ln_f(x)
+        x, _ = ops.fused_add_layernorm(x, delta, self.ln_f.weight,
+                                       self.ln_f.bias, self.ln_f.eps)
+        return x
+
     def _run_blocks(self, x, mask_bias, seg):
+        if self.mx_active:
+            return self._run_blocks_mx(x, mask_bias, seg)
         drop, attn_drop = self._dropout_args()
         if drop is not None:
             delta = None

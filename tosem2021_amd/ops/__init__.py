@@ -8,6 +8,7 @@ never pass on a non-native path.
 from __future__ import annotations
 
 import os
+import warnings
 from typing import Optional
 
 import torch
@@ -989,3 +990,217 @@ def adamw_step_grouped_clipped(p, grad, m, v, master, seg_end, seg_lr_mult,
         reference.adamw_step_grouped_clipped(
             p, grad, m, v, master, seg_end, seg_lr_mult, seg_wd, lr, beta1,
             beta2, eps, step, clip_state)
+
+
+# ---- MXFP8 serving (off by default; docs/KERNELS.md "MXFP8 operands") --------
+# OCP MXFP8 operands for the four projections of an encoder block at
+# inference: e4m3fn elements with one e8m0 power-of-two scale per 32
+# consecutive elements of K, as reference.mx_quantize defines them.  A
+# quantised tensor travels as (q, s): uint8 e4m3 bytes shaped like the tensor
+# it stands for and uint8 e8m0 bytes [..., K / 32].  On the GPU the producers
+# are HIP kernels that match the reference bit for bit and the GEMM is a
+# library call (mx_gemm_backend); on the CPU every op is built from the
+# reference, so a quantised model runs there as a fake-quant simulation.  No
+# autograd.
+
+def mx_quant_rows(x):
+    """(q, s) = MXFP8 of x [..., K] along K, K % 32 == 0: activations on
+    their way into a projection, and weights [N, K]."""
+    if x.is_cuda:
+        return tuple(hip_ops().mx_quant_rows(x.contiguous()))
+    return reference.mx_quantize(x)
+
+
+def mx_layernorm(x, gamma, beta, eps: float = 1e-5):
+    """(q, s) = mx_quant_rows(fused_layernorm(x, gamma, beta, eps)), bit for
+    bit, in one kernel that never writes the bf16 activations.  D % 32 == 0
+    and D <= 4096 on the GPU."""
+    if x.is_cuda:
+        q, s, _ = hip_ops().mx_layernorm_fwd(x.contiguous(), None, gamma,
+                                             beta, eps)
+        return q, s
+    return reference.mx_quantize(
+        reference.layernorm_fwd(x, gamma, beta, eps)[0])
+
+
+def mx_add_layernorm(x, residual, gamma, beta, eps: float = 1e-5):
+    """(q, s, sum) with (y, sum) = fused_add_layernorm(x, residual, gamma,
+    beta, eps) and (q, s) = mx_quant_rows(y), bit for bit."""
+    if x.is_cuda:
+        return tuple(hip_ops().mx_layernorm_fwd(
+            x.contiguous(), residual.contiguous(), gamma, beta, eps))
+    y, sm, _, _ = reference.add_layernorm_fwd(x, residual, gamma, beta, eps)
+    return (*reference.mx_quantize(y), sm)
+
+
+def mx_bias_gelu(h, b):
+    """(q, s) = mx_quant_rows(fused_bias_gelu(h, b)), bit for bit, in one
+    kernel: the down projection's operand from the up GEMM's bias-free bf16
+    output."""
+    if h.is_cuda:
+        return tuple(hip_ops().mx_bias_gelu(h.contiguous(), b))
+    return reference.mx_quantize(reference.bias_gelu_fwd(h, b))
+
+
+def mx_supported(M: int, N: int, K: int) -> bool:
+    """The (rows, out features, in features) lattice of mx_linear on the
+    GPU: what the block-scaled GEMM of the installed library takes."""
+    return (M > 0 and N > 0 and K > 0 and M % 32 == 0 and N % 32 == 0
+            and K % 128 == 0)
+
+
+def _mx_pad_scale_rows(s2):
+    """torch._scaled_mm takes the scales of an [R, K] operand as
+    round_up(R, 128) * K / 32 bytes: plain row-major [R, K / 32] with the
+    rows filled up (2^0 scales for rows that do not exist)."""
+    pad = -s2.shape[0] % 128
+    if not pad:
+        return s2
+    return torch.cat([s2, s2.new_full((pad, s2.shape[1]), 127)])
+
+
+def _mx_scaled_mm(q2, s2, wq, ws, bias=None):
+    return torch._scaled_mm(
+        q2.view(torch.float8_e4m3fn), wq.view(torch.float8_e4m3fn).t(),
+        _mx_pad_scale_rows(s2).view(torch.float8_e8m0fnu),
+        _mx_pad_scale_rows(ws).view(torch.float8_e8m0fnu),
+        bias=bias, out_dtype=torch.bfloat16)
+
+
+def _mx_dequant_linear(q2, s2, wq, ws, bias=None):
+    return torch.nn.functional.linear(
+        reference.mx_dequantize(q2, s2).to(torch.bfloat16),
+        reference.mx_dequantize(wq, ws).to(torch.bfloat16), bias)
+
+
+# (GEMM backend, whether its own bias argument is used), probed once.
+#
+# MEASUREMENT-ONLY on the library this was written against (torch 2.10 /
+# ROCm 7 on MI355X): there the probe turns the block-scaled GEMM down (it
+# truncates its bf16 output and takes no bias, docs/PERF.md "MXFP8
+# serving"), so _mx_scaled_mm, the scale-row padding and the separate bias
+# add run only under TOSEM_MX_GEMM=scaled_mm, for scripts/bench_mx_serving.py,
+# and in tests/test_mx_gpu.py's test of that branch under the wider budget a
+# truncating output needs.  They become the default path by themselves on a
+# library whose block-scaled GEMM meets the contract.
+_MX_BACKEND: Optional[tuple] = None
+# shapes the block-scaled GEMM refused at run time (each reported once by a
+# warning): they take the dequantised GEMM from then on
+_MX_REFUSED: set = set()
+
+
+def _mx_probe() -> tuple:
+    """(plain GEMM within the contract, GEMM with bias within the contract).
+    Run the block-scaled GEMM once, without and with its bias argument,
+    on operands whose block scales differ within every row, and hold it to
+    mx_linear's accuracy contract against float64 of the dequantised
+    operands: per output 2^-8 |y| (the bf16 rounding or its neighbour) plus
+    K 2^-24 sum_k |a_k w_k| (an f32 accumulation in any order).  A build
+    without the MX path raises; one that read the scales in another layout
+    than row-major [rows, K / 32] misses by orders of magnitude."""
+    g = torch.Generator().manual_seed(0)
+    M, N, K = 96, 160, 256
+
+    def operand(R):
+        e = torch.randint(-8, 9, (R, K // 32), generator=g).float()
+        x = torch.randn(R, K, generator=g) * torch.exp2(e).repeat_interleave(
+            32, 1)
+        return reference.mx_quantize(x.bfloat16())
+
+    (aq, asc), (wq, wsc) = operand(M), operand(N)
+    a64 = reference.mx_dequantize(aq, asc).double()
+    w64 = reference.mx_dequantize(wq, wsc).double()
+    ref = a64 @ w64.t()
+    acc = K * 2.0 ** -24 * (a64.abs() @ w64.abs().t())
+    bias = (torch.randn(N, generator=g) * ref.std()).bfloat16()
+    dev_ops = [t.cuda() for t in (aq, asc, wq, wsc)]
+
+    def within(b):
+        want = ref if b is None else ref + b.double()
+        try:
+            y = _mx_scaled_mm(*dev_ops, None if b is None else b.cuda())
+        except (RuntimeError, AttributeError, TypeError):
+            return False
+        err = (y.double().cpu() - want).abs()
+        return bool((err <= 2.0 ** -8 * want.abs() + acc).all())
+
+    return within(None), within(bias)
+
+
+def _mx_backend() -> tuple:
+    global _MX_BACKEND
+    if _MX_BACKEND is None:
+        force = os.environ.get("TOSEM_MX_GEMM", "")
+        if force == "dequant":
+            _MX_BACKEND = ("dequant", True)
+        else:
+            ok, ok_bias = _mx_probe()
+            # the dequantised GEMM takes its bias in F.linear
+            _MX_BACKEND = (("scaled_mm", ok_bias)
+                           if ok or force == "scaled_mm" else
+                           ("dequant", True))
+    return _MX_BACKEND
+
+
+def mx_gemm_backend() -> str:
+    """Which GEMM mx_linear runs on the GPU: "scaled_mm" (torch._scaled_mm's
+    block-scaled hipBLASLt GEMM on the MXFP8 operands themselves) or
+    "dequant" (operands dequantised to bf16, exact except for values below
+    bf16's range, then F.linear: no speed to claim).  Probed once per
+    process against mx_linear's accuracy contract (_mx_probe): a block-scaled
+    GEMM that misses it is not used.  A/B knob: TOSEM_MX_GEMM=dequant or
+    =scaled_mm forces one of them, the latter whatever the probe found."""
+    return _mx_backend()[0]
+
+
+def mx_bias_in_gemm() -> bool:
+    """Whether mx_linear's bias goes through the GEMM's own bias argument
+    (one rounding to bf16) or, where the library does not take one in this
+    mode, through one torch add on the GEMM's bf16 output."""
+    return _mx_backend()[1]
+
+
+def mx_linear(q, s, wq, ws, bias=None, out_dtype=None):
+    """y [..., N] = dequant(q, s) [..., K] @ dequant(wq, ws) [N, K]^T + bias,
+    f32 accumulation.  GPU: bf16 out, through mx_gemm_backend(); (rows, N, K)
+    off mx_supported's lattice raises ValueError.  CPU: F.linear of the
+    dequantised operands in f32, cast to out_dtype (default f32)."""
+    K = q.shape[-1]
+    N = wq.shape[0]
+    lead = q.shape[:-1]
+    if wq.shape[-1] != K or s.shape != (*lead, K // 32) or \
+            ws.shape != (N, K // 32):
+        raise ValueError("mx_linear operands disagree: q "
+                         f"{tuple(q.shape)}, s {tuple(s.shape)}, wq "
+                         f"{tuple(wq.shape)}, ws {tuple(ws.shape)}")
+    if not q.is_cuda:
+        y = torch.nn.functional.linear(
+            reference.mx_dequantize(q, s), reference.mx_dequantize(wq, ws),
+            None if bias is None else bias.float())
+        return y if out_dtype is None else y.to(out_dtype)
+    if out_dtype not in (None, torch.bfloat16):
+        raise ValueError(f"mx_linear on the GPU writes bf16, not {out_dtype}")
+    M = q.numel() // K
+    if not mx_supported(M, N, K):
+        raise ValueError(
+            "mx_linear on the GPU needs rows and out features that are "
+            "multiples of 32 and in features a multiple of 128, got "
+            f"(M, N, K) = ({M}, {N}, {K})")
+    q2 = q.reshape(M, K)
+    s2 = s.reshape(M, K // 32)
+    backend, bias_in_gemm = _mx_backend()
+    if backend == "scaled_mm" and (M, N, K) not in _MX_REFUSED:
+        try:
+            y = _mx_scaled_mm(q2, s2, wq, ws, bias if bias_in_gemm else None)
+            if bias is not None and not bias_in_gemm:
+                y = y + bias
+            return y.view(*lead, N)
+        except RuntimeError as e:
+            # the library has no block-scaled kernel for this shape: say so,
+            # once, and serve it through the dequantised GEMM
+            warnings.warn(
+                f"mx_linear: the block-scaled GEMM refused (M, N, K) = "
+                f"({M}, {N}, {K}) and the dequantised GEMM takes this shape "
+                f"from now on: {str(e).splitlines()[0]}")
+            _MX_REFUSED.add((M, N, K))
+    return _mx_dequant_linear(q2, s2, wq, ws, bias).view(*lead, N)

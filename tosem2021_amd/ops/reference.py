@@ -441,3 +441,39 @@ def cross_entropy_bwd(logits: torch.Tensor, target: torch.Tensor,
     d = p * grow.unsqueeze(1)
     return torch.where(valid.unsqueeze(1), d, torch.zeros_like(d)).to(
         logits.dtype)
+
+
+MX_BLOCK = 32       # elements of K that share one e8m0 scale
+
+
+def mx_quantize(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """OCP MXFP8 along the last dim: x [..., K] (finite, K % 32 == 0) ->
+    (q uint8 [..., K] holding e4m3fn bytes, s uint8 [..., K / 32] holding
+    e8m0 bytes).  Per block of 32 consecutive elements, with E the biased f32
+    exponent field of the largest magnitude: s = clamp(E - 8, 0, 254), meaning
+    the scale 2^(s - 127), and q = e4m3fn(clamp(x * 2^(127 - s), -448, 448)),
+    round to nearest even, subnormals kept.  The clamp comes before the
+    conversion: a scaled magnitude reaches (448, 512) whenever the block
+    maximum's mantissa is above 1.75, and the conversion alone would make it
+    NaN.  This is the definition the HIP kernels (csrc/mx.h) match bit for
+    bit."""
+    K = x.shape[-1]
+    if K == 0 or K % MX_BLOCK:
+        raise ValueError(f"MXFP8 needs K % {MX_BLOCK} == 0, got K = {K}")
+    xb = x.float().reshape(*x.shape[:-1], K // MX_BLOCK, MX_BLOCK)
+    amax = xb.abs().amax(dim=-1)
+    E = (amax.view(torch.int32) >> 23) & 0xFF
+    s = (E - 8).clamp(0, 254)
+    # 2^(127 - s) has the exponent field 254 - s >= 1: a normal f32
+    mul = ((254 - s) << 23).view(torch.float32)
+    q = (xb * mul.unsqueeze(-1)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    return q.view(torch.uint8).reshape(x.shape), s.to(torch.uint8)
+
+
+def mx_dequantize(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """f32 [..., K] = e4m3fn(q) * 2^(s - 127) per block of 32; exact."""
+    K = q.shape[-1]
+    qf = q.view(torch.float8_e4m3fn).float()
+    sf = s.view(torch.float8_e8m0fnu).float()
+    return (qf.reshape(*q.shape[:-1], K // MX_BLOCK, MX_BLOCK)
+            * sf.unsqueeze(-1)).reshape(q.shape)

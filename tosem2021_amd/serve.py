@@ -39,11 +39,17 @@ class ClassifierService:
                  model: str = "mltc-base", seq: int = 256,
                  threshold: float = 0.5, device: Optional[str] = None,
                  repo_prefix: bool = False, pack: bool = False,
-                 use_ema: bool = False):
+                 use_ema: bool = False, mx: bool = False):
         # pack: run one request's texts as a packed batch (data.packing)
         # use_ema: serve the weight average the checkpoint carries (a run
         # with ema_decay > 0); ValueError if it carries none
+        # mx: MXFP8 projections (MLTC.quantize_mx), quantised once here from
+        # the weights just loaded, the average included when use_ema
+        if mx and not ckpt_dir:
+            raise ValueError("mx=True needs a trained model (ckpt_dir): the "
+                             "rules+lexicon backend has nothing to quantise")
         self.pack = pack
+        self.mx = mx
         self.seq = seq
         self.threshold = threshold
         self.repo_prefix = repo_prefix
@@ -69,11 +75,26 @@ class ClassifierService:
                 load_ema_weights(self.trainer,
                                  Trainer.latest_checkpoint(ckpt_dir))
             self.trainer.model.eval()
+            if mx:
+                self.trainer.model.quantize_mx()
             self.tok = CodeTokenizer(cfg.vocab_size)
 
     @property
     def backend(self) -> str:
         return "mltc" if self.trainer is not None else "rules+lexicon"
+
+    @property
+    def precision(self) -> Dict[str, Optional[str]]:
+        """What /healthz reports: the projections' precision and, for
+        MXFP8 on the GPU, the GEMM behind ops.mx_linear."""
+        from tosem2021_amd import ops
+        if not self.mx:
+            dt = ("bf16" if self.device.type == "cuda" else "f32") \
+                if self.trainer is not None else None
+            return {"precision": dt, "mx_gemm_backend": None}
+        return {"precision": "mxfp8",
+                "mx_gemm_backend": ops.mx_gemm_backend()
+                if self.device.type == "cuda" else "reference"}
 
     @torch.no_grad()
     def classify(self, texts: List[str],
@@ -159,7 +180,7 @@ def build_app(ckpt_dir: Optional[str] = None, **kw):
     @app.get("/healthz")
     def healthz():
         return {"ok": True, "backend": svc.backend,
-                "device": str(svc.device)}
+                "device": str(svc.device), **svc.precision}
 
     @app.get("/metrics", response_class=PlainTextResponse)
     def metrics():

@@ -51,6 +51,10 @@ class FlatParams:
             self.flat[off:off + n].copy_(p.data.reshape(-1))
             p.data = self.flat[off:off + n].view(p.shape)
             p.grad = self.grad_flat[off:off + n].view(p.shape)
+            # the parameter keeps its own version counter: code that must
+            # notice writes through the flat buffer (MLTC.quantize_mx)
+            # reads the owner's
+            p._flat_owner = self.flat
             self.offsets.append(off)
             off += n
         self.params = params
@@ -267,6 +271,9 @@ class Trainer:
         else:
             ops.adamw_step(*bufs, grad_scale=grad_scale,
                            wd=c.weight_decay, **hp)
+        # the fused steps write through raw pointers: no version counter sees
+        # them, so count the write here (no kernel, no sync)
+        torch.autograd.graph.increment_version(f.flat)
 
     def _finish_step(self) -> dict:
         """Count the step as applied or skipped; returns the extra
